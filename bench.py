@@ -7,7 +7,8 @@ counters when N > 1). Inputs are the reference's own channel stream (minstd_rand
 libstdc++ distributions; rank r starts (2^31-2)/N draws after rank r-1 in it), generated on the host and resident in HBM
 before timing. Weak scaling: every rank decodes its own B codewords.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch G] [--full]
+                    [--dump-outputs DIR]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 `--gpus N` without a launcher (no WORLD_SIZE in the environment) starts the N rank processes
@@ -16,11 +17,18 @@ must equal the world size. `--batch B` is per rank (weak scaling, the default);
 `--global-batch G` fixes the job's total instead (strong scaling: G / N codewords per rank),
 which is how config 5's 2^20 words fit eight ranks' shares of the minstd_rand0 period.
 
-Rank 0 prints one JSON line (driver contract) with `roofline` (HIP-event kernel time of
-the dominant kernel vs the 8 TB/s HBM roof at 9n+8 algorithmic bytes per codeword),
-`points` (the same measurement at each Eb/N0 of --points: the FER/throughput curve) and
+Rank 0 prints one JSON line (driver contract). A plain run does only what the headline needs:
+the batch of the --snr point, W warmup + K timed steps, `value` / `ms_per_step` and the FER/op
+counters those K steps accumulated. `--full` adds the runs of their own: `roofline` and
+`kernels` (HIP-event kernel time of the dominant kernel vs the 8 TB/s HBM roof at 9n+8
+algorithmic bytes per codeword, from K more steps), `points` (the same measurement at each
+Eb/N0 of --points: the FER/throughput curve, counters from one more pass each) and
 `cpu_baseline` (the reference itself, compiled into oracle/_ref, one process per host core
 on disjoint ranges of the same stream, on a bounded sample of the same workload).
+
+`--dump-outputs DIR` writes what the last timed step of the --snr point left with its caller
+(rank 0's shard) as DIR/<name>.npy, see dump_outputs(). The inputs are a pure function of the
+arguments, so two builds run with the same arguments can be compared array for array.
 """
 import argparse
 import contextlib
@@ -72,7 +80,16 @@ def parse():
                          "same exchange staged through the host, e.g. several ranks on one GPU)")
     ap.add_argument("--unfused", action="store_true",
                     help="decode_device + count_device (re-reads res and stats) instead of the fused call")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: per-kernel times and "
+                         "roofline, the --points curve, the CPU baseline (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs (decoded words, path "
+                         "metrics, counters) to DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def load_pkg():
@@ -192,9 +209,51 @@ def cpu_baseline(args, gpu_rate, bchk):
             "gpu_over_cpu": round(gpu_rate / rate, 1) if rate > 0 else None}
 
 
-def run_point(args, bchk, dec, snr, world, rank, dist, dev):
+DUMP_RES_BYTES = 32 << 20  # float32 sample of the decoded words
+DUMP_ROW_CAP = 1 << 21     # rows of the per-row vectors (l0 in f64, res_weight in f32)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(out_dir, d_res, d_l0, d_cnt):
+    """The arrays the timed call handed back in its last step, as float .npy files (44 MB at
+    the default 2^20 x 63; at most 56 MB for any shape):
+      res.npy         f32 [R, n]  decoded words of R rows (all rows while they fit in
+                                  DUMP_RES_BYTES, else a fixed seeded sample, ascending)
+      res_weight.npy  f32 [B']    Hamming weight of every decoded word (every row of the batch
+                                  up to DUMP_ROW_CAP rows, else a fixed seeded sample)
+      l0.npy          f64 [B']    path metric of the same rows (DBL_MAX where nothing was accepted)
+      counters.npy    f64 [6]     the FER/op counters as accumulated over the timed steps
+    """
+    import numpy as np
+    import torch
+
+    B, n = d_res.shape
+    rng = np.random.default_rng(DUMP_SEED)
+
+    def sample(cap):
+        if B <= cap:
+            return None
+        return torch.from_numpy(np.sort(rng.choice(B, cap, replace=False))).to(d_res.device)
+
+    os.makedirs(out_dir, exist_ok=True)
+    rows = sample(max(1, DUMP_RES_BYTES // (4 * n)))
+    res = d_res if rows is None else d_res[rows]
+    np.save(os.path.join(out_dir, "res.npy"), res.cpu().numpy().astype(np.float32))
+    rows = sample(DUMP_ROW_CAP)
+    weight = d_res.sum(dim=1, dtype=torch.int32)
+    l0 = d_l0
+    if rows is not None:
+        weight, l0 = weight[rows], l0[rows]
+    np.save(os.path.join(out_dir, "res_weight.npy"), weight.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "l0.npy"), l0.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "counters.npy"), d_cnt.cpu().numpy().astype(np.float64))
+
+
+def run_point(args, bchk, dec, snr, world, rank, dist, dev, full, dump_dir=None):
     """One Eb/N0 point: the rank's batch generated into HBM, W warmup + K timed steps (max over
-    ranks), per-kernel HIP-event durations from K more steps, FER/op counters."""
+    ranks) and the counters they accumulated; `dump_dir`: the last timed step's outputs written
+    there; `full`: per-kernel HIP-event durations from K more steps and the FER/op counters of
+    one more pass."""
     import numpy as np
     import torch
 
@@ -260,6 +319,30 @@ def run_point(args, bchk, dec, snr, world, rank, dist, dev):
         elapsed = time.perf_counter() - t0
         if world > 1:
             dist.barrier()
+    elapsed = max_over_ranks(elapsed, world, dist, dev)
+    total_words = world * B * args.steps
+    value = total_words / elapsed
+    # the K timed steps decoded the same resident words K times: their accumulated counters
+    # are K times one pass (summed over ranks for N > 1)
+    timed_cnt = d_cnt.cpu().numpy().astype(np.int64)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, d_res, d_l0, d_cnt)
+    if not full:
+        cut_build = os.path.basename(bchk.LIB_PATH) != "libbchk.so" and bool(os.environ.get("BCHK_CUT_BUILD"))
+        complete = int(timed_cnt[5]) == total_words
+        assert complete or cut_build, "counters must cover every word once per step"
+        cnt = timed_cnt // args.steps
+        words = int(cnt[5])
+        return {
+            "snr_db": snr, "value": value, "ms_per_step": elapsed / args.steps * 1e3,
+            "fer": (int(cnt[0]) / words) if words else None,
+            "ber": (int(cnt[1]) / words / n) if words else None,
+            "decodes_per_codeword": (int(cnt[2]) / words) if words else None,
+            "frame_errors": int(cnt[0]), "words": words, "counters": [int(c) for c in cnt],
+            "counters_complete": complete, "cut_build": cut_build,
+            "host_generation_s": t_gen, "rank_draws": used, "rank_draw_budget": budget,
+        }
+    with on_stream():
         # per-kernel durations: the same steps again with HIP events around every launch
         # (outside the timed region, so event records do not perturb `value`)
         dec.profile(True)
@@ -281,7 +364,6 @@ def run_point(args, bchk, dec, snr, world, rank, dist, dev):
     n_exact, n_coop = dec.path_counts()
     n_tail = dec.tail_count()
     tail_stats = dec.tail_stats()
-    elapsed = max_over_ranks(elapsed, world, dist, dev)
     cnt = d_cnt.cpu().numpy().astype(np.int64)  # one pass over the batch, summed over ranks (N > 1)
     # every word counted once -- unless an experiment library that cuts a kernel short (it
     # finishes no word; scripts/gpu_first_cut.sh) is loaded instead of the product libbchk.so:
@@ -289,8 +371,6 @@ def run_point(args, bchk, dec, snr, world, rank, dist, dev):
     complete = int(cnt[5]) == world * B
     cut_build = os.path.basename(bchk.LIB_PATH) != "libbchk.so" and bool(os.environ.get("BCHK_CUT_BUILD"))
     assert complete or cut_build, "counters must cover every word once"
-    total_words = world * B * args.steps
-    value = total_words / elapsed
     # Algorithmic bytes per codeword: 8n B of f64 samples in, n B decoded bits and 8 B l0
     # out (9n + 8, the roofline's `achieved`); the fused step also reads the
     # n-B sent word for its counters (10n + 8, reported beside it as `achieved_fused`).
@@ -440,19 +520,21 @@ def main():
         dec = bchk.KanekoKernelProcessor(args.m, args.t, J=args.J, device=gpu)
         dev = torch.device("cuda", gpu)
     n, B = dec.n, args.batch
-    snrs = [float(x) for x in args.points.split(",") if x.strip()] if args.points else []
+    # a plain run: the headline point only; --full: every Eb/N0 of --points as well
+    snrs = [float(x) for x in args.points.split(",") if x.strip()] if args.points and args.full else []
     if args.snr not in snrs:
         snrs.append(args.snr)
-    pts = {snr: run_point(args, bchk, dec, snr, world, rank, dist, dev) for snr in sorted(snrs)}
+    pts = {snr: run_point(args, bchk, dec, snr, world, rank, dist, dev, args.full,
+                          args.dump_outputs if snr == args.snr else None) for snr in sorted(snrs)}
     head = pts[args.snr]
-    dom = next(k for k in head["kernels"] if k["name"] == head["dominant_kernel"])
+    dom = next(k for k in head["kernels"] if k["name"] == head["dominant_kernel"]) if args.full else None
     # HBM bytes per launch of the dominant kernel, from the committed PMC passes of the same
     # workload (scripts/gpu_final6.sh -> scripts/traffic_req_json.py, rocprofv3 --pmc memory-
     # side requests by size); null when no profile of this workload exists. It is a stored
     # measurement (rocprofv3 cannot run inside this process): its source is named. A stage of
     # two launches (lane pre-pass + first kernel) sums both.
     traffic, traffic_src, traffic_read = None, None, None
-    if os.path.exists(args.traffic):
+    if args.full and os.path.exists(args.traffic):
         try:
             tr = json.load(open(args.traffic))
             if tr.get("batch") == B and tr.get("snr_db") == args.snr and tr.get("J") == args.J:
@@ -491,6 +573,21 @@ def main():
             "fer": head["fer"],
             "ber": head["ber"],
             "decodes_per_codeword": head["decodes_per_codeword"],
+            "host_generation_s": round(head["host_generation_s"], 2),
+            "counters_complete": head["counters_complete"],
+            **({"cut_build": True} if head["cut_build"] else {}),
+            **({"stub_decoder": "tests/bench_stub.py (CPU oracle, plumbing test; not a measurement)"}
+               if stub else {}),
+            "rank_draws": head["rank_draws"], "rank_draw_budget": head["rank_draw_budget"],
+            "full": args.full,
+            **({"dumped_outputs": args.dump_outputs} if args.dump_outputs else {}),
+            # the points measured: a plain run's one, with the counters of its timed steps
+            "points": [{k: (round(p[k], 4 if k == "ms_per_step" else 3) if k in ("value", "ms_per_step") else p[k])
+                        for k in ("snr_db", "value", "ms_per_step", "fer", "frame_errors", "words", "counters",
+                                  "decodes_per_codeword")} for p in pts.values()],
+        }
+    if rank == 0 and args.full:
+        out.update({
             "kernels": head["kernels"],
             "dominant_kernel": head["dominant_kernel"],
             "kernel_ms_per_step": round(head["kernel_ms_per_step"], 4),
@@ -513,15 +610,10 @@ def main():
                         "dominant_kernel": p["dominant_kernel"], "frac": round(p["frac"], 6),
                         "kernels": p["kernels"], "tail": p["tail"]} for p in pts.values()],
             "tail": head["tail"],
-            "host_generation_s": round(head["host_generation_s"], 2),
-            "counters_complete": head["counters_complete"],
-            **({"cut_build": True} if head["cut_build"] else {}),
-            **({"stub_decoder": "tests/bench_stub.py (CPU oracle, plumbing test; not a measurement)"}
-               if stub else {}),
-            "rank_draws": head["rank_draws"], "rank_draw_budget": head["rank_draw_budget"],
-        }
+        })
         if world == 1 and not stub:
             out["cpu_baseline"] = cpu_baseline(args, head["value"], bchk)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -9,7 +9,7 @@ mkdir -p $OUT
 cd $ROOT
 : > $OUT/${TAG}.jsonl
 run() {
-  timeout -k 10 ${LIM:-200} python bench.py --cpu-seconds 0 "$@" >> $OUT/${TAG}.jsonl 2>> $OUT/${TAG}.err
+  timeout -k 10 ${LIM:-200} python bench.py --full --cpu-seconds 0 "$@" >> $OUT/${TAG}.jsonl 2>> $OUT/${TAG}.err
   rc=$?; echo "[$*] rc=$rc"; [ $rc -eq 0 ] || exit $rc
 }
 for S in 7 6; do run --m 8 --t 15 --snr $S --J -1 --steps 3 --warmup 1; done

@@ -27,13 +27,13 @@ IFS=';' read -ra BL <<< "$BENCHES"
 for b in "${BL[@]}"; do
   [ -n "${b// /}" ] || continue
   if [[ "$b" == *"|"* ]]; then ENVS=${b%%|*}; ARGS=${b#*|}; else ENVS=; ARGS=$b; fi
-  timeout -k 10 400 env $ENVS python bench.py $ARGS >> $OUT/${TAG}_bench.jsonl 2>> $OUT/${TAG}_bench.err
+  timeout -k 10 400 env $ENVS python bench.py --full $ARGS >> $OUT/${TAG}_bench.jsonl 2>> $OUT/${TAG}_bench.err
   rc=$?; echo "bench [$b] rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 if [ "$PROF" = rocprof ] && [ ${#BL[@]} -gt 0 ]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof -o run \
-      -- python3 $ROOT/bench.py --cpu-seconds 0 --points '' --steps 5 --warmup 1 ${BL[0]#*|} > $OUT/${TAG}_prof.log 2>&1
+      -- python3 $ROOT/bench.py --full --cpu-seconds 0 --points '' --steps 5 --warmup 1 ${BL[0]#*|} > $OUT/${TAG}_prof.log 2>&1
   rc=$?; echo "rocprof rc=$rc"; exit $rc
 fi
 exit 0

@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd $ROOT
 : > $OUT/${TAG}.jsonl
 run() {  # each configuration at its own Eb/N0 only (--points ''): the 4/5/6 dB curve is the headline's
-  timeout -k 10 240 python bench.py --cpu-seconds 0 --points '' "$@" >> $OUT/${TAG}.jsonl 2>> $OUT/${TAG}.err
+  timeout -k 10 240 python bench.py --full --cpu-seconds 0 --points '' "$@" >> $OUT/${TAG}.jsonl 2>> $OUT/${TAG}.err
   rc=$?; echo "[$*] rc=$rc"; [ $rc -eq 0 ] || exit $rc
 }
 [ "${ONLY_LONG:-0}" = 1 ] || {

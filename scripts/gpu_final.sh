@@ -10,17 +10,17 @@ cd $ROOT
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > $OUT/tests_$TAG.log 2>&1
 rc=$?; echo "tests rc=$rc"; tail -n 2 $OUT/tests_$TAG.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 300 python bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run \
-    -- python3 $ROOT/bench.py --cpu-seconds 0 --points 5 > $OUT/prof_$TAG.log 2>&1
+    -- python3 $ROOT/bench.py --full --cpu-seconds 0 --points 5 > $OUT/prof_$TAG.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
 i=0
 for CNT in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/traffic_${TAG}_p$i -o run \
-      -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --points 5 > $OUT/traffic_${TAG}_p$i.log 2>&1
+      -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --points 5 > $OUT/traffic_${TAG}_p$i.log 2>&1
   rc=$?; echo "pmc pass $i ($CNT) rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 $ROOT/scripts/pmc_summary.py $OUT/traffic_$TAG > $OUT/traffic_${TAG}_summary.json && echo summary ok

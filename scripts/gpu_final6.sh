@@ -20,21 +20,21 @@ pmc() {  # name, bench args: memory-side requests by size (reads, then writes), 
              "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum"; do
     i=$((i+1))
     timeout -s KILL 150 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/traffic_${nm}_p$i -o run \
-        -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --points '' "$@" > $OUT/traffic_${nm}_p$i.log 2>&1
+        -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --points '' "$@" > $OUT/traffic_${nm}_p$i.log 2>&1
     rc=$?; echo "pmc $nm pass $i rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done
 }
 ( cd /tmp && export TMPDIR=/tmp && pmc $TAG --snr 5 ) || exit 1
 python3 $ROOT/scripts/traffic_req_json.py $OUT/traffic_${TAG}_p1/run_counter_collection.csv $OUT/traffic_${TAG}_p2/run_counter_collection.csv 1048576 5.0 15 > $OUT/traffic_${TAG}.json && echo traffic json ok
-timeout -k 10 300 python bench.py --traffic $OUT/traffic_${TAG}.json > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 300 python bench.py --full --traffic $OUT/traffic_${TAG}.json > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run \
-    -- python3 $ROOT/bench.py --cpu-seconds 0 --points 5 > $OUT/prof_$TAG.log 2>&1
+    -- python3 $ROOT/bench.py --full --cpu-seconds 0 --points 5 > $OUT/prof_$TAG.log 2>&1
 rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd $ROOT
 # bench.py --gpus 2 without a launcher: it spawns its two ranks (gloo: both on the box's one GPU)
-timeout -k 10 300 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 1 --points '' --cpu-seconds 0 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err
+timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 1 --points '' --cpu-seconds 0 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err
 rc=$?; echo "bench --gpus 2 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 [ -n "${CONFIG5:-}" ] || exit 0
 : > $OUT/${TAG}_255.jsonl
@@ -43,7 +43,7 @@ for PT in "5 15" "6 -1" "7 15"; do
   nm=${TAG}_255_${1}dB
   ( cd /tmp && export TMPDIR=/tmp && pmc $nm --m 8 --t 15 --snr $1 --J $2 ) || exit 1
   python3 $ROOT/scripts/traffic_req_json.py $OUT/traffic_${nm}_p1/run_counter_collection.csv $OUT/traffic_${nm}_p2/run_counter_collection.csv 1048576 $1.0 $2 > $OUT/traffic_${nm}.json
-  timeout -k 10 400 python bench.py --m 8 --t 15 --snr $1 --J $2 --points '' --steps 5 --warmup 1 --cpu-seconds 12 \
+  timeout -k 10 400 python bench.py --full --m 8 --t 15 --snr $1 --J $2 --points '' --steps 5 --warmup 1 --cpu-seconds 12 \
       --traffic $OUT/traffic_${nm}.json >> $OUT/${TAG}_255.jsonl 2>> $OUT/${TAG}_255.err
   rc=$?; echo "[255 $PT] rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done

@@ -21,7 +21,7 @@ n=fp['codewords']; print('first pass per codeword', {k: round(v/n) for k,v in fp
 cd /tmp && export TMPDIR=/tmp
 CNT="SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD GRBM_GUI_ACTIVE"
 timeout -s KILL 120 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/${TAG}_sq1 -o run \
-    -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 --points '' > $OUT/${TAG}_sq1.log 2>&1
+    -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 --points '' > $OUT/${TAG}_sq1.log 2>&1
 rc=$?; echo "sq rc=$rc"; [ $rc -eq 0 ] || exit $rc
 cd $ROOT
 for k in kaneko_search_kernel kaneko_fast_ring; do echo "== $k"; python scripts/sq_summary.py $OUT/${TAG} $k; done

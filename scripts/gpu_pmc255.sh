@@ -13,6 +13,6 @@ for CNT in "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WA
            "SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAVES"; do
   i=$((i+1))
   eval timeout -s KILL 150 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/${TAG}_p$i -o run \
-      -- python3 $ROOT/bench.py $ARGS > $OUT/${TAG}_p$i.log 2>&1
+      -- python3 $ROOT/bench.py --full $ARGS > $OUT/${TAG}_p$i.log 2>&1
   rc=$?; echo "pmc pass $i rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done

@@ -14,10 +14,10 @@ if [ -n "$K" ]; then
   [ $rc -eq 0 ] || exit $rc
 fi
 if [ -n "${SPAWN2:-}" ]; then
-  timeout -k 10 300 python bench.py --gpus 2 --backend gloo --steps 5 --warmup 1 --points '' --cpu-seconds 0 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err
+  timeout -k 10 300 python bench.py --full --gpus 2 --backend gloo --steps 5 --warmup 1 --points '' --cpu-seconds 0 > $OUT/bench2_$TAG.json 2> $OUT/bench2_$TAG.err
   rc=$?; echo "bench --gpus 2 rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 300 python bench.py --cpu-seconds ${CPUS:-0} ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+timeout -k 10 300 python bench.py --full --cpu-seconds ${CPUS:-0} ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || exit $rc
 python - $OUT/bench_$TAG.json <<'PY'
 import json,sys

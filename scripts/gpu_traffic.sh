@@ -12,7 +12,7 @@ i=0
 for CNT in FETCH_SIZE WRITE_SIZE; do
   i=$((i+1))
   timeout -s KILL 120 rocprofv3 --pmc $CNT --kernel-trace --output-format csv -d $OUT/${TAG}_p$i -o run \
-      -- python3 $ROOT/bench.py --steps 2 --warmup 1 --cpu-seconds 0 "$@" > $OUT/${TAG}_p$i.log 2>&1
+      -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --cpu-seconds 0 "$@" > $OUT/${TAG}_p$i.log 2>&1
   rc=$?; echo "pass $i ($CNT) rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 $ROOT/scripts/pmc_summary.py $OUT/$TAG > $OUT/${TAG}_summary.json && echo summary ok

@@ -34,7 +34,7 @@ def free_port():
 
 
 BENCH_ARGS = ["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--points", "",
-              "--cpu-seconds", "0"]  # BCH(63,30,13) at 5 dB: bench.py's defaults
+              "--cpu-seconds", "0", "--full"]  # BCH(63,30,13) at 5 dB: bench.py's defaults
 # (no --m / --t: torch.distributed.run's parser would take them as abbreviations of its own)
 
 

@@ -45,7 +45,7 @@ def shard_counters(m, t, J, snr, B, world, seed=1):
 
 
 COMMON = ["--m", "5", "--t", "3", "--snr", "3.0", "--points", "", "--steps", "2", "--warmup", "1",
-          "--cpu-seconds", "0", "--backend", "gloo"]
+          "--cpu-seconds", "0", "--backend", "gloo", "--full"]  # --full: the line's `points`
 
 
 def test_gpus3_spawns_three_ranks_one_line_counters_equal_shards():
@@ -93,6 +93,56 @@ def test_single_rank_default_line():
     assert rec["n_gpus"] == 1 and rec["config"]["launch"] == "single"
     want = shard_counters(5, 3, 15, 3.0, 256, 1)
     np.testing.assert_array_equal(np.array(rec["points"][0]["counters"], np.int64), want)
+
+
+def test_plain_run_is_the_headline_only_and_dumps_outputs(tmp_path):
+    """Without --full: the headline's point alone with the headline fields, none of the
+    fields that take runs of their own, and --dump-outputs writes float arrays whose counters
+    are the K timed steps' sums (so --steps is the number of timed steps)."""
+    B, K = 200, 3
+    plain = [a for a in COMMON if a != "--full"]
+    plain[plain.index("--steps") + 1] = str(K)
+    out = run_bench(["--gpus", "1", "--batch", str(B), "--dump-outputs", str(tmp_path / "o")] + plain)
+    assert out.returncode == 0, out.stderr[-4000:]
+    (rec,) = json_lines(out)
+    assert rec["full"] is False and rec["steps"] == K and rec["n_gpus"] == 1
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in rec
+    assert rec["unit"] == "codewords/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    assert rec["value"] == pytest.approx(B / (rec["ms_per_step"] * 1e-3), rel=1e-3)
+    for key in ("kernels", "roofline", "cpu_baseline", "tail"):
+        assert key not in rec
+    want = shard_counters(5, 3, 15, 3.0, B, 1)
+    (point,) = rec["points"]  # the headline's point alone, its counters from the timed steps
+    np.testing.assert_array_equal(np.array(point["counters"], np.int64), want)
+    assert point["snr_db"] == 3.0 and point["words"] == B and "kernels" not in point
+    assert rec["counters_complete"] and rec["fer"] == want[0] / B
+    got = {f: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert sorted(got) == ["counters.npy", "l0.npy", "res.npy", "res_weight.npy"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    np.testing.assert_array_equal(got["counters.npy"], (K * want).astype(np.float64))
+    assert got["res.npy"].shape == (B, 31) and got["l0.npy"].shape == (B,)
+    assert got["res_weight.npy"].shape == (B,)
+
+
+def test_dump_sample_is_fixed_and_bounded(monkeypatch, tmp_path):
+    """A batch past the caps: the dumped rows are the same seeded sample on every call."""
+    import torch
+    monkeypatch.setattr(bench, "DUMP_RES_BYTES", 4 * 7 * 10)
+    monkeypatch.setattr(bench, "DUMP_ROW_CAP", 50)
+    rng = np.random.default_rng(3)
+    res = torch.from_numpy(rng.integers(0, 2, (300, 7), dtype=np.uint8))
+    l0 = torch.from_numpy(rng.standard_normal(300))
+    cnt = torch.arange(6, dtype=torch.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), res, l0, cnt)
+    a = {f: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    for f, arr in a.items():
+        np.testing.assert_array_equal(arr, np.load(tmp_path / "b" / f))
+    assert a["res.npy"].shape == (10, 7) and a["l0.npy"].shape == (50,)
+    idx = np.flatnonzero(np.isin(l0.numpy(), a["l0.npy"]))
+    np.testing.assert_array_equal(a["l0.npy"], l0.numpy()[idx])
+    np.testing.assert_array_equal(a["res_weight.npy"], res.numpy()[idx].sum(axis=1))
 
 
 @pytest.mark.parametrize("world", [2, 4, 8])
