@@ -298,9 +298,19 @@ int bchk_polar_decode_device(bchk_polar *pc, const float *d_llr, size_t B, uint8
  * one codeword's list decode can take seconds, so a decode call is a series of kernel launches
  * of about 50 ms each (environment BCHK_POLAR_BUDGET_MS; 0 = one launch per call): a codeword
  * is suspended between two search items and resumed by the next launch, with identical
- * results. Such a call returns when the batch is decoded (it synchronises its stream). The
- * launches the last call took (1 for codes without a search layer or with the budget off). */
+ * results. A budgeted decode call is synchronous on the stream it is given: it waits for
+ * that stream after every launch and returns when the batch is decoded (bchk_polar_decode_device
+ * too, on the caller's stream). One context must not be used from two streams (or threads) at
+ * once: the per-codeword states, the save slots of suspended codewords and the launch counters
+ * belong to the context. Every launch makes progress whatever the budget (a wave always works on
+ * the first unfinished codeword it meets, and a search runs at least one round per launch); a
+ * launch that leaves codewords unfinished and reports none is an error (BCHK_EHIP), not a hang.
+ * The launches the last call took (1 for codes without a search layer or with the budget off). */
 int bchk_polar_last_launches(const bchk_polar *pc, uint64_t *launches);
+/* Device scratch the context holds for budgeted calls, in bytes: 4 per codeword of the largest
+ * batch so far, one save slot of *save_stride bytes (may be NULL; 0 for codes without a search
+ * layer) per workgroup of the largest grid so far, and two counter words. */
+int bchk_polar_scratch_bytes(const bchk_polar *pc, uint64_t *bytes, uint64_t *save_stride);
 /* CMixedKernelEncoder::Encode (MixedKernelEncoder.cpp:142-177), host side: info [B][K] ->
  * codewords [B][N]. */
 int bchk_polar_encode_host(const bchk_polar *pc, const uint8_t *info, size_t B, uint8_t *cw);

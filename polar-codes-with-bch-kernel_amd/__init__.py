@@ -39,6 +39,7 @@ EXPORTS = (
     "bchk_syndrome_table_query", "bchk_syndrome_table_info", "bchk_polar_create", "bchk_polar_create_kdir",
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
+    "bchk_polar_scratch_bytes",
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
     "bchk_kernel_column_search", "bchk_last_error", "bchk_version",
 )
@@ -120,6 +121,7 @@ def lib():
     L.bchk_polar_sync.argtypes = [vp]
     L.bchk_polar_stream.argtypes = [vp]
     L.bchk_polar_stream.restype = vp
+    L.bchk_polar_scratch_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.bchk_syndrome_table_query.argtypes = [i32, i32, vp, sz, vp, vp]
     L.bchk_syndrome_table_info.argtypes = [i32, i32, C.POINTER(u64), C.POINTER(u64),
                                            C.POINTER(C.c_uint32)]
@@ -438,6 +440,12 @@ class PolarListDecoder:
         n = C.c_uint64()
         _check(lib().bchk_polar_last_launches(self._h, C.byref(n)))
         return n.value
+
+    def scratch_bytes(self):
+        """(device scratch held for budgeted calls, bytes of one workgroup's save slot)."""
+        b, s = C.c_uint64(), C.c_uint64()
+        _check(lib().bchk_polar_scratch_bytes(self._h, C.byref(b), C.byref(s)))
+        return b.value, s.value
 
 
 def stream_skip(k, n, state, words):

@@ -91,13 +91,22 @@ struct PolarMixedParams {
     // items (its LDS state and registers to rsave, rstate[cw] = 1) and starts no other; the
     // host launches again until `unfinished` stays 0. rstate: 0 not started, 1 suspended,
     // 2 done. budget 0 (or rstate null): every codeword runs to its end in one launch.
+    // A wave always starts (or resumes) the first unfinished codeword it meets in a launch,
+    // whatever the clock says, and a search runs at least one round per launch: every launch
+    // that leaves codewords unfinished has done work (`progress` > 0), however small the budget.
+    // A wave has at most one suspended codeword -- after suspending it starts nothing more, and
+    // the next launch (same grid) resumes it before anything else -- so rsave holds one slot
+    // per workgroup, not per codeword.
     uint32_t *rstate;
-    uint8_t *rsave;
-    uint32_t rstride;       // bytes of rsave per codeword (polar_mixed_save_bytes)
+    uint8_t *rsave;         // [grid][rstride]
+    uint32_t rstride;       // bytes of rsave per workgroup (polar_mixed_save_bytes)
     uint32_t *unfinished;   // codewords left suspended or not started by this launch
+    uint32_t *progress;     // search rounds (at least), items and codewords completed by this launch
     uint64_t budget;
     int32_t no_mid;         // experiments: suspend between search items only (BCHK_POLAR_NO_MID)
+    uint32_t ml_rounds;     // a search past this many rounds in all gives NaN (BCHK_POLAR_ML_ROUNDS)
 };
+constexpr uint32_t kMlRoundsDefault = 1u << 20;
 
 // The kernel's LDS offsets (polar_mixed.hip), shared with the host's save-area size.
 struct PolarMixedLayout {

@@ -103,6 +103,12 @@ struct bchk_polar {
 
 namespace {
 
+// bytes of one workgroup's save slot (a suspended codeword, polar_device.h)
+uint32_t polar_save_stride(const bchk_polar *c) {
+    const PolarMixedParams &m = c->mp;
+    return polar_mixed_save_bytes(polar_mixed_layout(c->U, c->L, m.ssize, m.csize, m.osize, m.nl, polar_rec_words(c->K)));
+}
+
 // The specification (MixedKernelEncoder.cpp:7-98): header, kernel names, shortened and
 // punctured symbols, then U - K freezing constraints "w t_1 ... t_w" (ascending, the frozen
 // symbol last). The GPU decoder takes Arikan layers ("A"); other kernels are rejected.
@@ -390,6 +396,9 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         int tmin = 16, mlmin = kPolarMaxTrellisKernel + 1;
         if (const char *e = getenv("BCHK_POLAR_TRELLIS")) tmin = std::max(2, atoi(e));
         if (const char *e = getenv("BCHK_POLAR_ML")) mlmin = std::max(2, atoi(e));
+        // the search's round guard (a finite tree: never reached in practice; tests lower it)
+        m.ml_rounds = kMlRoundsDefault;
+        if (const char *e = getenv("BCHK_POLAR_ML_ROUNDS")) m.ml_rounds = (uint32_t)std::max(1L, atol(e));
         m.any_ml = 0;
         m.tstates = 0;
         c->tbase.assign((size_t)nl * kPolarMaxKernel, 0u);
@@ -513,6 +522,13 @@ int bchk_polar_last_launches(const bchk_polar *c, uint64_t *launches) {
     return 0;
 }
 
+int bchk_polar_scratch_bytes(const bchk_polar *c, uint64_t *bytes, uint64_t *save_stride) {
+    if (!c || !bytes) return pfail(BCHK_EINVAL, "NULL argument");
+    *bytes = (uint64_t)c->rstate.cap + c->rsave.cap + c->unfinished.cap;
+    if (save_stride) *save_stride = (c->mixed && c->mp.any_ml) ? polar_save_stride(c) : 0;
+    return 0;
+}
+
 int bchk_polar_params(const bchk_polar *c, int *n, int *k, int *unshortened, int *list_size) {
     if (!c) return pfail(BCHK_EINVAL, "NULL argument");
     if (n) *n = c->N;
@@ -575,27 +591,35 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         // ~budget each (plus one search item): a wave suspends its codeword between two items
         // past the budget and the next launch resumes it (same results, bit for bit: the
         // state saved is the whole list state). The call returns when every codeword is done.
-        const PolarMixedLayout ol = polar_mixed_layout(c->U, c->L, m.ssize, m.csize, m.osize, m.nl, polar_rec_words(c->K));
-        const uint32_t stride = polar_mixed_save_bytes(ol);
+        // A workgroup has at most one suspended codeword (PolarMixedParams), and the grid is
+        // the same for every launch of the call: one save slot per workgroup.
+        const uint32_t stride = polar_save_stride(c);
         int rc;
-        if ((rc = c->rstate.ensure(B * 4)) || (rc = c->rsave.ensure(B * (size_t)stride)) ||
-            (rc = c->unfinished.ensure(4)))
+        if ((rc = c->rstate.ensure(B * 4)) || (rc = c->rsave.ensure((size_t)grid * stride)) ||
+            (rc = c->unfinished.ensure(8)))
             return rc;
         PHIP_TRY(hipMemsetAsync(c->rstate.p, 0, B * 4, s));
         m.rstate = (uint32_t *)c->rstate.p;
         m.rsave = (uint8_t *)c->rsave.p;
         m.rstride = stride;
-        m.unfinished = (uint32_t *)c->unfinished.p;
+        m.unfinished = (uint32_t *)c->unfinished.p;  // two words: unfinished, progress
+        m.progress = m.unfinished + 1;
         m.budget = c->budget_ticks;
         m.no_mid = getenv("BCHK_POLAR_NO_MID") ? 1 : 0;
         for (uint64_t launch = 0;; ++launch) {
-            PHIP_TRY(hipMemsetAsync(c->unfinished.p, 0, 4, s));
+            PHIP_TRY(hipMemsetAsync(c->unfinished.p, 0, 8, s));
             PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
-            uint32_t left = 0;
-            PHIP_TRY(hipMemcpyAsync(&left, c->unfinished.p, 4, hipMemcpyDeviceToHost, s));
+            uint32_t left[2] = {0, 0};
+            PHIP_TRY(hipMemcpyAsync(left, c->unfinished.p, 8, hipMemcpyDeviceToHost, s));
             PHIP_TRY(hipStreamSynchronize(s));
             c->launches_last = launch + 1;
-            if (left == 0) break;
+            if (left[0] == 0) break;
+            // every launch that leaves work does some (the kernel starts or resumes a wave's
+            // first unfinished codeword whatever the clock says): no progress is a kernel fault,
+            // reported instead of launching for ever
+            if (left[1] == 0)
+                return pfail(BCHK_EHIP, "budgeted SC-list decode made no progress in launch %llu (%u codewords left)",
+                             (unsigned long long)(launch + 1), left[0]);
         }
         return 0;
     }

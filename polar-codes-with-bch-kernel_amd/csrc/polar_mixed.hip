@@ -191,27 +191,32 @@ struct MlResume {
     int sp;
     float best0, best1;
     uint64_t hd, lrb;
+    uint32_t rounds;  // rounds done so far (the guard below counts the whole search)
 };
 
 // rs == null: the whole search in this call. Otherwise *resume says whether the scratch and
 // *rs hold a suspended search to continue, and past the deadline (t_launch + budget on the
 // 100 MHz clock), after at least one round of this call, the search stops between two rounds:
-// *rs filled, *suspended set, the return value meaningless.
+// *rs filled, *suspended set, the return value meaningless. max_rounds: the guard on the
+// search's rounds in all, over every launch it took.
 __device__ float ml_llr(const uint64_t *kr, int l, int loc, const float *src, const uint8_t *off, int d, int s,
-                        int lane, const MlScratch &ms, MlResume *rs = nullptr, bool resume = false,
-                        uint64_t t_launch = 0, uint64_t budget = 0, bool *suspended = nullptr) {
+                        int lane, const MlScratch &ms, uint32_t max_rounds, MlResume *rs = nullptr,
+                        bool resume = false, uint64_t t_launch = 0, uint64_t budget = 0,
+                        bool *suspended = nullptr) {
     const float kInf = __int_as_float(0x7F800000);
     const uint64_t lt = (1ull << lane) - 1ull;
     const int nf = l - loc - 1;
     uint64_t hd, lrb;
     float best0, best1;
     int sp;
+    uint32_t rounds = 0;
     if (rs && resume) {
         hd = rs->hd;
         lrb = rs->lrb;
         best0 = rs->best0;
         best1 = rs->best1;
         sp = rs->sp;
+        rounds = rs->rounds;
     } else {
         // the layer's LLRs with the known inputs' sign flips (:240-262), HD = Y < 0 (:270-276)
         float a = 0.0f;
@@ -294,15 +299,17 @@ __device__ float ml_llr(const uint64_t *kr, int l, int loc, const float *src, co
         sp = 2;
         wsync();
     }
-    // a guard only (the search tree is finite): past 2^20 rounds the LLR is NaN, never a hang
-    for (uint32_t rounds = 0; sp > 0; ++rounds) {
-        if (rounds >= (1u << 20)) return __int_as_float(0x7FC00000);
-        if (rs && rounds > 0 && __builtin_amdgcn_s_memrealtime() - t_launch > budget) {
+    // a guard only (the search tree is finite): past max_rounds rounds (2^20; counted over
+    // every launch the search took) the LLR is NaN, never a hang
+    for (const uint32_t first = rounds; sp > 0; ++rounds) {
+        if (rounds >= max_rounds) return __int_as_float(0x7FC00000);
+        if (rs && rounds > first && __builtin_amdgcn_s_memrealtime() - t_launch > budget) {
             rs->sp = sp;  // past the launch's deadline: stop between two rounds
             rs->best0 = best0;
             rs->best1 = best1;
             rs->hd = hd;
             rs->lrb = lrb;
+            rs->rounds = rounds;
             *suspended = true;
             return 0.0f;
         }
@@ -392,14 +399,23 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     const bool budgeted = p.budget != 0 && p.rstate != nullptr;
     const uint64_t t_launch = __builtin_amdgcn_s_memrealtime();
     auto expired = [&]() { return budgeted && __builtin_amdgcn_s_memrealtime() - t_launch > p.budget; };
+    // Liveness under any budget: the first unfinished codeword a wave meets in a launch is
+    // started (or resumed) whatever the clock says, so the clock only stops a wave that has
+    // worked in this launch. `stop` is sticky: after a suspension or the first skip the wave
+    // starts nothing more, so the codewords of its stride are, in order, finished ones, at most
+    // one suspended one, then untouched ones -- which is what lets the save slot be the wave's.
+    bool worked = false, stop = false;
+    uint32_t prog = 0;  // search rounds (one counted per suspended search), items, codewords done
+    uint8_t *const sv = budgeted ? p.rsave + (size_t)blockIdx.x * p.rstride : nullptr;
     for (uint32_t cw = blockIdx.x; cw < p.B; cw += gridDim.x) {
         const uint32_t cst = budgeted ? __builtin_amdgcn_readfirstlane(p.rstate[cw]) : 0u;
         if (cst == 2u) continue;  // finished by an earlier launch
-        if (expired()) {          // past the budget: start (or resume) nothing more
+        if (stop || (worked && expired())) {  // past the budget: start (or resume) nothing more
+            stop = true;
             if (lane == 0) atomicAdd(p.unfinished, 1u);
             continue;
         }
-        uint8_t *sv = budgeted ? p.rsave + (size_t)cw * p.rstride : nullptr;
+        worked = true;
         uint32_t active;
         float R = 0.0f, lv = 0.0f;
         uint64_t dm = 0;
@@ -439,7 +455,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
         bool progressed = false, yielded = false;
         // suspend between two search items (the list state is complete there: every layer
         // before rj done, layer rj's offset state applied, items before it done)
-        MlResume mr{0, 0.0f, 0.0f, 0ull, 0ull};
+        MlResume mr{0, 0.0f, 0.0f, 0ull, 0ull, 0u};
         bool rmid = false;  // resuming inside a search item (its scratch saved too)
         if (cst == 1u) {
             const uint32_t *hd = reinterpret_cast<const uint32_t *>(sv);
@@ -453,6 +469,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[11]) << 32);
                 mr.lrb = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[12]) |
                          ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[13]) << 32);
+                mr.rounds = (uint32_t)__builtin_amdgcn_readfirstlane(hd[14]);
                 const uint8_t *ml = sv + 64 + 64 * 24 + o_ph + (o_tm - o_act);
                 const int mb = (int)kMlHeadBytes + 12 * mr.sp;  // G, U, cost, ay, stack[0, sp)
                 for (int i = 4 * lane; i < mb; i += 256) *reinterpret_cast<uint32_t *>(mls + i) = *reinterpret_cast<const uint32_t *>(ml + i);
@@ -477,6 +494,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                 hd[11] = (uint32_t)(mr.hd >> 32);
                 hd[12] = (uint32_t)mr.lrb;
                 hd[13] = (uint32_t)(mr.lrb >> 32);
+                hd[14] = mr.rounds;
             }
             if (mid) {
                 uint8_t *ml = sv + 64 + 64 * 24 + o_ph + (o_tm - o_act);
@@ -498,8 +516,11 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             if (lane == 0) {
                 p.rstate[cw] = 1u;
                 atomicAdd(p.unfinished, 1u);
+                if (prog) atomicAdd(p.progress, prog);
             }
+            prog = 0;
             yielded = true;
+            stop = true;
         };
         for (int phi = phi0; phi < U && !yielded; ++phi) {
             const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)ph[phi]);
@@ -561,9 +582,10 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                         const int q = (int)act[it / d], s = it % d;
                         const bool mid = resume_here && it == rit && rmid;  // continue a suspended search
                         bool susp = false;
-                        const float v = ml_llr(kr, l, loc, Sof(q, j), Oof(q, j), d, s, lane, ms,
+                        const float v = ml_llr(kr, l, loc, Sof(q, j), Oof(q, j), d, s, lane, ms, p.ml_rounds,
                                                budgeted && !p.no_mid ? &mr : nullptr, mid, t_launch, p.budget,
                                                &susp);
+                        ++prog;      // the item, or (suspended) the one round or more it ran
                         if (susp) {  // the search itself ran past the budget: suspended inside it
                             suspend(phi, j, it, true);
                             break;
@@ -792,7 +814,11 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             if (lane == 0) p.metric[row] = rdlf_m(R, q);
         }
         if (lane == 0) p.count[cw] = nact;
-        if (budgeted && lane == 0) p.rstate[cw] = 2u;
+        if (budgeted && lane == 0) {
+            p.rstate[cw] = 2u;
+            atomicAdd(p.progress, prog + 1u);
+        }
+        prog = 0;
         wsync();
     }
 }
