@@ -317,6 +317,61 @@ int bchk_polar_encode_host(const bchk_polar *pc, const uint8_t *info, size_t B, 
 int bchk_polar_sync(bchk_polar *pc);
 void *bchk_polar_stream(bchk_polar *pc);
 
+/* ---- Polar FER simulation on the device: the AWGN/BPSK part of the vendored simulator's
+ * iteration (out/external/Simulator.cpp:104-110, :139-335, headers/external/Modem.h:64-78) as
+ * kernels (csrc/polar_channel.hip). Device pointers; each call enqueues on `stream` (NULL =
+ * the context's stream); B = 0 is a no-op; B > 2^32 - 1 is BCHK_EINVAL. */
+/* CMixedKernelEncoder::Encode (MixedKernelEncoder.cpp:142-177) as a kernel, bit for bit
+ * bchk_polar_encode_host for every code bchk_polar_create accepts: d_info [B][K] -> d_cw [B][N]. */
+int bchk_polar_encode_device(bchk_polar *pc, const uint8_t *d_info, size_t B, uint8_t *d_cw, void *stream);
+/* Words [word0, word0 + B) of a counter-based stream (Philox4x32-10 keyed by seed, the
+ * generator of bchk_generate_device; word w depends only on (seed, w)) at Eb/N0 snr_db:
+ * uniform information bits (counter (w low, w high, 0xFFFFFFFF, index of the 128-bit block)),
+ * the codeword, BPSK with bit 1 -> +1 (Modem.h:64), y = x + sigma z in double with sigma =
+ * sqrt(0.5 10^(-snr_db/10) N / K) (Simulator.cpp:108, N the transmitted length; z for flat
+ * element G = w N + position is one of the Box-Muller pair of counter (G / 2, tag 0x5EED)),
+ * LLR = (float)(-2 y / sigma^2) (Modem.h:78; positive favours 0). d_info [B][K] and d_cw
+ * [B][N] may each be NULL; d_llr [B][N] float. Statistically the simulator's stream, NOT its
+ * GSL mt19937 stream bit for bit (the same caveat as bchk_generate_device). */
+int bchk_polar_generate_device(bchk_polar *pc, double snr_db, size_t B, uint64_t seed, uint64_t word0,
+                               uint8_t *d_info, uint8_t *d_cw, float *d_llr, void *stream);
+/* The counters of CSimulator::Iterate (Simulator.cpp:201-318) for one decoded batch -- sent
+ * d_info_tx [B][K], d_cw_tx [B][N], the channel's d_llr [B][N], and bchk_polar_decode_device's
+ * d_info [B][L][K], d_cw [B][L][N] (required: the counters need the codeword rows), d_count
+ * [B] -- added into the device array d_out8 (uint64_t[8]):
+ *   [0] words
+ *   [1] block errors: row 0's information bits differ from the sent ones, or count <= 0 (:233-255)
+ *   [2] information bit errors of row 0, over block-error words (:245-249, :283)
+ *   [3] code bit errors of row 0, over block-error words (:250-254, :284)
+ *   [4] ML errors: block error, count > 0 and CurCorr >= MLCorr, the double sums of +-llr[i]
+ *       over i = 0..N-1 in index order (:264-287)
+ *   [5] list errors: block error and the sent codeword is not among rows 1..count-1 (:263, :288-318)
+ *   [6] raw bit errors: positions where (sent bit ? -llr : llr) < 0 (:203-208)
+ *   [7] words with count <= 0
+ * A word with count <= 0 adds to [0], [1], [5], [6] and [7] only: the reference would compare
+ * the stale buffers of the previous word there. d_flags ([B] bytes, may be NULL) receives per
+ * word bit 0 = block error, bit 1 = ML error, bit 2 = list error. */
+int bchk_polar_count_device(bchk_polar *pc, const uint8_t *d_info_tx, const uint8_t *d_cw_tx, const float *d_llr,
+                            const uint8_t *d_info, const uint8_t *d_cw, const int32_t *d_count, size_t B,
+                            uint64_t *d_out8, uint8_t *d_flags, void *stream);
+/* One Eb/N0 point of bchk_polar_sweep_device: the counters of bchk_polar_count_device. */
+typedef struct bchk_polar_point {
+    double snr_db;
+    uint64_t c[8];
+} bchk_polar_point;
+/* The simulation loop end to end on the device: `points` points at snr_from + i snr_step into
+ * the host array out; each generates (bchk_polar_generate_device, stream `seed`), decodes and
+ * counts batches of at most `batch` words (0 = sized from the context's grid) until max_words
+ * words or max_errors block errors. A point is cut exactly in word order: its counters cover
+ * the words up to and including the one that carries the max_errors-th block error, and the
+ * word index runs on across points (the next point starts at the word after the cut), so the
+ * records are a function of the arguments other than `batch`. Synchronous, on the context's
+ * stream, with buffers the context owns; seconds (may be NULL) = wall time, words_decoded (may
+ * be NULL) = words sent through the decoder (whole batches, the cut ones included). */
+int bchk_polar_sweep_device(bchk_polar *pc, double snr_from, double snr_step, int points, uint64_t max_words,
+                            uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
+                            double *seconds, uint64_t *words_decoded);
+
 /* ---- BCH polar-kernel construction and the column-permutation search (root bchCoder.cpp;
  * csrc/kernel_search.hip). Kernels are row-major l x l bytes (0/1). */
 /* makeMatrix (root bchCoder.cpp:356-389): the nested extended-BCH kernel of size 2^power

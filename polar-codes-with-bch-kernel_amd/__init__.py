@@ -39,10 +39,16 @@ EXPORTS = (
     "bchk_syndrome_table_query", "bchk_syndrome_table_info", "bchk_polar_create", "bchk_polar_create_kdir",
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
-    "bchk_polar_scratch_bytes",
+    "bchk_polar_scratch_bytes", "bchk_polar_encode_device", "bchk_polar_generate_device",
+    "bchk_polar_count_device", "bchk_polar_sweep_device",
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
     "bchk_kernel_column_search", "bchk_last_error", "bchk_version",
 )
+
+# struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device
+POLAR_POINT_DTYPE = np.dtype([("snr_db", "<f8"), ("c", "<u8", (8,))])
+POLAR_COUNTERS = ("words", "block_errors", "info_bit_errors", "code_bit_errors", "ml_errors", "list_errors",
+                  "raw_bit_errors", "no_decision")
 
 STATS_DTYPE = np.dtype([("decodes", "<u8"), ("comparisons", "<u8"), ("sums", "<u8"),
                         ("iterations", "<u8"), ("jsteps", "<u8"), ("improvements", "<u8"),
@@ -122,6 +128,11 @@ def lib():
     L.bchk_polar_stream.argtypes = [vp]
     L.bchk_polar_stream.restype = vp
     L.bchk_polar_scratch_bytes.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
+    L.bchk_polar_encode_device.argtypes = [vp, vp, sz, vp, vp]
+    L.bchk_polar_generate_device.argtypes = [vp, dbl, sz, u64, u64, vp, vp, vp, vp]
+    L.bchk_polar_count_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp, vp]
+    L.bchk_polar_sweep_device.argtypes = [vp, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
+                                          C.POINTER(u64)]
     L.bchk_syndrome_table_query.argtypes = [i32, i32, vp, sz, vp, vp]
     L.bchk_syndrome_table_info.argtypes = [i32, i32, C.POINTER(u64), C.POINTER(u64),
                                            C.POINTER(C.c_uint32)]
@@ -381,7 +392,8 @@ class KanekoKernelProcessor:
 class PolarListDecoder:
     """CMixedKernelListDecoder(Spec, ListSize) + Decode (out/external/MixedKernelListDecoder.cpp
     :9, :211-268) on the GPU: batched SC-list decoding of a polar code given by the
-    reference's specification text (Arikan layers)."""
+    reference's specification text (Arikan layers), and the AWGN/BPSK simulation around it
+    (encode_device, generate_device, count_device, sweep_device: out/external/Simulator.cpp)."""
 
     def __init__(self, spec, L, device=0, kernel_dir=None):
         h = C.c_void_p()
@@ -431,6 +443,35 @@ class PolarListDecoder:
     def decode_device(self, d_llr, B, d_info, d_cw, d_metric, d_count, stream=None):
         _check(lib().bchk_polar_decode_device(self._h, d_llr, B, d_info, d_cw, d_metric, d_count,
                                               stream))
+
+    def encode_device(self, d_info, B, d_cw, stream=None):
+        """The encoder on the GPU: d_info [B][K] u8 -> d_cw [B][N] u8 (device pointers)."""
+        _check(lib().bchk_polar_encode_device(self._h, d_info or None, B, d_cw or None, stream))
+
+    def generate_device(self, snr_db, B, d_llr, d_info=None, d_cw=None, seed=1, word0=0, stream=None):
+        """On-GPU channel: words [word0, word0 + B) of the counter-based stream at Eb/N0 snr_db into
+        d_llr [B][N] f32 and, where given, d_info [B][K] and d_cw [B][N]."""
+        _check(lib().bchk_polar_generate_device(self._h, snr_db, B, seed, word0, d_info or None, d_cw or None,
+                                                d_llr or None, stream))
+
+    def count_device(self, d_info_tx, d_cw_tx, d_llr, d_info, d_cw, d_count, B, d_out8, d_flags=None,
+                     stream=None):
+        """The simulator's counters of one decoded batch added into d_out8 (device uint64[8],
+        POLAR_COUNTERS); d_flags [B] u8 (optional): bit 0 block, 1 ML, 2 list error."""
+        _check(lib().bchk_polar_count_device(self._h, d_info_tx or None, d_cw_tx or None, d_llr or None,
+                                             d_info or None, d_cw or None, d_count or None, B, d_out8 or None,
+                                             d_flags or None, stream))
+
+    def sweep_device(self, snr_from, snr_step, points, max_words, max_errors, seed=1, batch=0):
+        """The FER simulation end to end on the GPU: ([(snr_db, counters [8] ints)], seconds,
+        words decoded). Each point runs until max_words words or max_errors block errors, cut
+        exactly in word order; the word index runs on across points."""
+        out = np.zeros(max(points, 0), POLAR_POINT_DTYPE)
+        secs, words = C.c_double(0.0), C.c_uint64(0)
+        _check(lib().bchk_polar_sweep_device(self._h, snr_from, snr_step, points, max_words, max_errors, seed,
+                                             batch, _p(out) if points > 0 else None, C.byref(secs),
+                                             C.byref(words)))
+        return [(float(r["snr_db"]), [int(v) for v in r["c"]]) for r in out], secs.value, words.value
 
     def sync(self):
         _check(lib().bchk_polar_sync(self._h))

@@ -15,34 +15,11 @@
 
 #include "bchk_device.h"
 #include "bchk_launch.h"
+#include "bchk_philox.h"
 
 namespace bchk {
 
 namespace {
-
-struct U4 {
-    uint32_t x, y, z, w;
-};
-
-// Philox4x32-10 (Salmon et al., SC'11): 10 rounds of the 4x32 bijection keyed by (k0, k1)
-__device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t h0 = __umulhi(M0, c.x), l0 = M0 * c.x;
-        const uint32_t h1 = __umulhi(M1, c.z), l1 = M1 * c.z;
-        c = U4{h1 ^ c.y ^ k0, l1, h0 ^ c.w ^ k1, l0};
-        k0 += W0;
-        k1 += W1;
-    }
-    return c;
-}
-
-// (0, 1] with 53 random bits
-__device__ __forceinline__ double unit53(uint32_t a, uint32_t b) {
-    const uint64_t v = ((uint64_t)a << 21) ^ (uint64_t)(b >> 11);  // 53 bits
-    return ((double)(v & ((1ull << 53) - 1ull)) + 1.0) * 0x1p-53;
-}
 
 constexpr int kChanWaves = 4;
 constexpr int kMaxWords64 = 4;  // n <= 255

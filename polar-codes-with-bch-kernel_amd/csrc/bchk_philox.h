@@ -1,0 +1,49 @@
+// bchk_philox.h -- the counter-based generator of the on-GPU channel front-ends
+// (bchk_channel.hip for BCH words, polar_channel.hip for polar words). Device code only.
+//
+// Counter layout of a (seed, word) stream, keyed by (seed low, seed high):
+//   information bits of word w, 128 at a time:  (w low, w high, 0xFFFFFFFF, block)
+//   noise of flat element G = w * n + position: one of the Box-Muller pair of counter
+//                                               (G / 2 low, G / 2 high, 0x5EED, 0)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace bchk {
+
+struct U4 {
+    uint32_t x, y, z, w;
+};
+
+// Philox4x32-10 (Salmon et al., SC'11): 10 rounds of the 4x32 bijection keyed by (k0, k1)
+__device__ __forceinline__ U4 philox(U4 c, uint32_t k0, uint32_t k1) {
+    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t h0 = __umulhi(M0, c.x), l0 = M0 * c.x;
+        const uint32_t h1 = __umulhi(M1, c.z), l1 = M1 * c.z;
+        c = U4{h1 ^ c.y ^ k0, l1, h0 ^ c.w ^ k1, l0};
+        k0 += W0;
+        k1 += W1;
+    }
+    return c;
+}
+
+// (0, 1] with 53 random bits
+__device__ __forceinline__ double unit53(uint32_t a, uint32_t b) {
+    const uint64_t v = ((uint64_t)a << 21) ^ (uint64_t)(b >> 11);  // 53 bits
+    return ((double)(v & ((1ull << 53) - 1ull)) + 1.0) * 0x1p-53;
+}
+
+// the standard normal pair of noise counter `pair` (elements 2 pair and 2 pair + 1)
+__device__ __forceinline__ void normal_pair(uint64_t pair, uint32_t k0, uint32_t k1, double z[2]) {
+    const U4 r = philox(U4{(uint32_t)pair, (uint32_t)(pair >> 32), 0x5EEDu, 0u}, k0, k1);
+    const double u1 = unit53(r.x, r.y), u2 = unit53(r.z, r.w);
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincospi(2.0 * u2, &sn, &cs);
+    z[0] = rad * cs;
+    z[1] = rad * sn;
+}
+
+}  // namespace bchk

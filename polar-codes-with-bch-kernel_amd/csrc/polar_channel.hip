@@ -1,0 +1,270 @@
+// polar_channel.hip -- the simulation front-end of the polar SC-list decoder: the AWGN/BPSK
+// part of the vendored simulator's iteration (out/external/Simulator.cpp:104-110, :139-335,
+// headers/external/Modem.h:64-78) as batched kernels, so that a FER experiment never leaves
+// the device. The words are statistically the simulator's (uniform information bits, Gaussian
+// noise of its standard deviation), drawn from the counter-based generator of bchk_philox.h
+// instead of its sequential GSL stream: word w of a (seed, Eb/N0) stream depends only on
+// (seed, w).
+//
+// polar_gen_kernel: one wave per word, u as packed bits in LDS. CMixedKernelEncoder::Encode
+// (out/external/MixedKernelEncoder.cpp:142-177): the information bits go to the unfrozen
+// symbols (64 symbols per ballot), static frozen symbols are zeros, the dynamic constraints
+// are walked in symbol order (a frozen symbol may depend on an earlier frozen one), their
+// terms reduced across the lanes; then the layers, innermost first: an Arikan layer whose
+// stride is a power of two is an XOR butterfly on the packed words, in place (shift and mask
+// within a dword below 32, whole dwords above); any other layer is the l x l GF(2) product
+// per block against the krows masks, 64 output symbols per ballot into the second buffer.
+// The transmitted symbols are then stored as bytes, and (generate) element G = word * N +
+// position of the stream takes one of the Box-Muller pair of counter G / 2.
+//
+// polar_count_kernel: one wave per decoded word, CSimulator::Iterate's counters
+// (Simulator.cpp:201-318); CurCorr and MLCorr of an errored word are summed in double in
+// index order, as the reference forms them, so that its `>=` is reproduced.
+#include <hip/hip_runtime.h>
+
+#include "bchk_philox.h"
+#include "polar_device.h"
+
+namespace bchk {
+
+namespace {
+
+// LDS written by some lanes of the wave is read by others after this
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ uint32_t ubit(const uint32_t *u, int pos) { return (u[pos >> 5] >> (pos & 31)) & 1u; }
+
+__global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGenParams p) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t psm[];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const PolarEncTables &t = p.t;
+    const int U = t.U, N = t.N, K = t.K;
+    const int u64s = (U + 63) / 64, kq = 2 * ((K + 127) / 128) + 2;
+    uint64_t *ib = reinterpret_cast<uint64_t *>(psm + (size_t)wid * polar_gen_wave_bytes(U, K));  // [kq]
+    uint64_t *ua = ib + kq, *ub = ua + u64s;                                                       // [u64s] each
+    const uint64_t nwaves = (uint64_t)gridDim.x * kPolarChanWaves;
+    for (uint64_t w = (uint64_t)blockIdx.x * kPolarChanWaves + (uint64_t)wid; w < (uint64_t)p.B; w += nwaves) {
+        const uint64_t word = p.word0 + w;
+        // ---- information bits, packed: bit r of the word = bit r & 63 of ib[r >> 6]
+        if (p.gen) {
+            for (int blk = lane; blk * 128 < K; blk += 64) {
+                const U4 r = philox(U4{(uint32_t)word, (uint32_t)(word >> 32), 0xFFFFFFFFu, (uint32_t)blk},
+                                    p.seed_lo, p.seed_hi);
+                ib[2 * blk] = (uint64_t)r.x | ((uint64_t)r.y << 32);
+                ib[2 * blk + 1] = (uint64_t)r.z | ((uint64_t)r.w << 32);
+            }
+        } else {
+            const uint8_t *in = p.info_in + w * (uint64_t)K;
+            for (int g = 0; g * 64 < K; ++g) {
+                const int r = g * 64 + lane;
+                const uint64_t m = __ballot(r < K && (in[r] & 1));
+                if (lane == 0) ib[g] = m;
+            }
+        }
+        wave_sync();
+        if (p.gen && p.info) {
+            uint8_t *out = p.info + w * (uint64_t)K;
+            for (int r = lane; r < K; r += 64) out[r] = (uint8_t)((ib[r >> 6] >> (r & 63)) & 1ull);
+        }
+        // ---- u: information bits at the unfrozen symbols, zeros at the frozen ones
+        for (int g = 0; g < u64s; ++g) {
+            const int i = g * 64 + lane;
+            const int r = i < U ? (int)t.inforank[i] : -1;
+            const uint64_t m = __ballot(r >= 0 && ((ib[r >> 6] >> (r & 63)) & 1ull));
+            if (lane == 0) ua[g] = m;
+        }
+        wave_sync();
+        // ---- dynamic frozen symbols in symbol order: the XOR of the constraint's earlier terms
+        {
+            uint32_t *u32 = reinterpret_cast<uint32_t *>(ua);
+            for (int d = 0; d < t.ndyn; ++d) {
+                const uint32_t a = t.dynoff[d], e = t.dynoff[d + 1] - 1u;  // terms [a, e), the symbol at e
+                uint32_t v = 0;
+                for (uint32_t q = a + (uint32_t)lane; q < e; q += 64) v ^= ubit(u32, t.dynterm[q]);
+                const uint32_t par = (uint32_t)__popcll(__ballot(v != 0)) & 1u;
+                const int sym = t.dynterm[e];
+                if (par && lane == 0) u32[sym >> 5] |= 1u << (sym & 31);
+                wave_sync();
+            }
+        }
+        // ---- the transform, innermost layer first (MixedKernelEncoder.cpp:159-170): each block
+        // of `next` symbols, viewed as l rows of `stride`, becomes (rows) x K
+        uint64_t *src = ua, *dst = ub;
+        for (int layer = t.nl - 1, stride = 1; layer >= 0; --layer) {
+            const int l = t.ksize[layer], next = stride * l;
+            const uint64_t *kr = t.krows + (size_t)layer * kPolarMaxKernel;
+            uint32_t *s32 = reinterpret_cast<uint32_t *>(src);
+            if (l == 2 && kr[0] == 1ull && kr[1] == 3ull && (stride & (stride - 1)) == 0) {
+                // Arikan: u[b] ^= u[b + stride] where (b & stride) == 0
+                if (stride < 32) {
+                    const uint32_t M = stride == 1 ? 0x55555555u : stride == 2 ? 0x33333333u
+                                     : stride == 4 ? 0x0F0F0F0Fu : stride == 8 ? 0x00FF00FFu : 0x0000FFFFu;
+                    for (int d = lane; d < 2 * u64s; d += 64) {
+                        const uint32_t x = s32[d];
+                        s32[d] = x ^ ((x >> stride) & M);
+                    }
+                } else {  // U is a multiple of 2 stride >= 64
+                    const int sd = stride >> 5, pairs = U >> 6;
+                    for (int q = lane; q < pairs; q += 64) {
+                        const int d = (q / sd) * 2 * sd + (q % sd);
+                        s32[d] ^= s32[d + sd];
+                    }
+                }
+            } else {
+                for (int g = 0; g < u64s; ++g) {
+                    const int pos = g * 64 + lane;
+                    uint32_t acc = 0;
+                    if (pos < U) {
+                        const int b0 = pos / next * next, rem = pos - b0, i = rem / stride, s2 = rem - i * stride;
+                        for (int j = 0; j < l; ++j)
+                            if ((kr[j] >> i) & 1ull) acc ^= ubit(s32, b0 + j * stride + s2);
+                    }
+                    const uint64_t m = __ballot(acc != 0);
+                    if (lane == 0) dst[g] = m;
+                }
+                uint64_t *tmp = src;
+                src = dst;
+                dst = tmp;
+            }
+            wave_sync();
+            stride = next;
+        }
+        // ---- the transmitted symbols, and LLR = -2 y / var of y = BPSK + sigma z
+        const uint32_t *c32 = reinterpret_cast<const uint32_t *>(src);
+        if (p.cw) {
+            uint8_t *cw = p.cw + w * (uint64_t)N;
+            for (int i = lane; i < N; i += 64) cw[i] = (uint8_t)ubit(c32, t.cwpos[i]);
+        }
+        if (p.gen) {
+            // global element G = word * N + position; the Box-Muller pair of counter G / 2 gives
+            // elements 2 p and 2 p + 1 (a pair may straddle two words: each wave computes it)
+            float *llr = p.llr + w * (uint64_t)N;
+            const uint64_t ebase = word * (uint64_t)N;
+            const uint64_t p0 = ebase >> 1, pend = (ebase + (uint64_t)N + 1) >> 1;
+            for (uint64_t pr = p0 + (uint64_t)lane; pr < pend; pr += 64) {
+                double z[2];
+                normal_pair(pr, p.seed_lo, p.seed_hi, z);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int64_t el = (int64_t)(2 * pr + (uint64_t)h) - (int64_t)ebase;  // within the word
+                    if (el < 0 || el >= (int64_t)N) continue;
+                    const double x = ubit(c32, t.cwpos[el]) ? 1.0 : -1.0;  // Modem.h:64
+                    const double y = x + p.sigma * z[h];
+                    llr[el] = (float)(-2.0 * y / p.var);  // Modem.h:78
+                }
+            }
+        }
+        wave_sync();  // the next word overwrites the buffers
+    }
+}
+
+__global__ void __launch_bounds__(64 * kPolarChanWaves) polar_count_kernel(PolarCountParams p) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int N = p.N, K = p.K, L = p.L;
+    unsigned long long c[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // wave-uniform
+    const uint64_t nwaves = (uint64_t)gridDim.x * kPolarChanWaves;
+    for (uint64_t w = (uint64_t)blockIdx.x * kPolarChanWaves + (uint64_t)wid; w < (uint64_t)p.B; w += nwaves) {
+        const float *llr = p.llr + w * (uint64_t)N;
+        const uint8_t *ctx = p.cw_tx + w * (uint64_t)N, *itx = p.info_tx + w * (uint64_t)K;
+        const uint8_t *info0 = p.info + w * (uint64_t)L * (uint64_t)K, *cw0 = p.cw + w * (uint64_t)L * (uint64_t)N;
+        int cnt = p.count[w];
+        if (cnt > L) cnt = L;
+        // raw bit errors (:203-208)
+        uint32_t raw = 0;
+        for (int i0 = 0; i0 < N; i0 += 64) {
+            const int i = i0 + lane;
+            bool e = false;
+            if (i < N) {
+                const float v = llr[i];
+                e = (ctx[i] ? -v : v) < 0.0f;
+            }
+            raw += (uint32_t)__popcll(__ballot(e));
+        }
+        c[0] += 1;
+        c[6] += raw;
+        uint32_t fl = 0;
+        if (cnt <= 0) {  // no decision: a block and list error; nothing to compare
+            c[1] += 1;
+            c[5] += 1;
+            c[7] += 1;
+            fl = 1u | 4u;
+        } else {
+            uint32_t ibe = 0, cbe = 0;  // row 0 against the sent word (:245-254)
+            for (int i0 = 0; i0 < K; i0 += 64) {
+                const int i = i0 + lane;
+                ibe += (uint32_t)__popcll(__ballot(i < K && ((info0[i] != 0) != (itx[i] != 0))));
+            }
+            if (ibe) {
+                for (int i0 = 0; i0 < N; i0 += 64) {
+                    const int i = i0 + lane;
+                    cbe += (uint32_t)__popcll(__ballot(i < N && ((cw0[i] != 0) != (ctx[i] != 0))));
+                }
+                c[1] += 1;
+                c[2] += ibe;
+                c[3] += cbe;
+                fl = 1u;
+                // MLCorr / CurCorr (:265-271): double sums of +-llr in index order
+                double ml = 0.0, cur = 0.0;
+                for (int i0 = 0; i0 < N; i0 += 64) {
+                    const int i = i0 + lane;
+                    const float v = i < N ? llr[i] : 0.0f;
+                    const uint64_t mt = __ballot(i < N && ctx[i] != 0), md = __ballot(i < N && cw0[i] != 0);
+                    const int m = N - i0 < 64 ? N - i0 : 64;
+                    for (int j = 0; j < m; ++j) {
+                        const float vj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
+                        ml += (double)(((mt >> j) & 1ull) ? -vj : vj);
+                        cur += (double)(((md >> j) & 1ull) ? -vj : vj);
+                    }
+                }
+                if (cur >= ml) {  // :286
+                    c[4] += 1;
+                    fl |= 2u;
+                }
+                bool found = false;  // the sent codeword among rows 1 .. count - 1 (:288-305)
+                for (int r = 1; r < cnt && !found; ++r) {
+                    const uint8_t *row = cw0 + (size_t)r * (size_t)N;
+                    bool diff = false;
+                    for (int i0 = 0; i0 < N && !diff; i0 += 64) {
+                        const int i = i0 + lane;
+                        diff = __ballot(i < N && ((row[i] != 0) != (ctx[i] != 0))) != 0ull;
+                    }
+                    found = !diff;
+                }
+                if (!found) {
+                    c[5] += 1;
+                    fl |= 4u;
+                }
+            }
+        }
+        if (p.flags && lane == 0) p.flags[w] = (uint8_t)fl;
+    }
+    if (lane == 0)
+        for (int q = 0; q < 8; ++q)
+            if (c[q]) atomicAdd(p.out8 + q, c[q]);
+}
+
+int chan_grid(uint32_t B) {
+    const uint32_t blocks = (B + kPolarChanWaves - 1) / kPolarChanWaves;
+    return (int)(blocks < 2048u ? blocks : 2048u);  // the waves stride over the rest
+}
+
+}  // namespace
+
+hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s) {
+    if (p.B == 0) return hipSuccess;
+    const size_t lds = (size_t)kPolarChanWaves * polar_gen_wave_bytes(p.t.U, p.t.K);  // <= 25 KiB at U = K = 16384
+    hipLaunchKernelGGL(polar_gen_kernel, dim3(chan_grid(p.B)), dim3(64 * kPolarChanWaves), lds, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s) {
+    if (p.B == 0) return hipSuccess;
+    hipLaunchKernelGGL(polar_count_kernel, dim3(chan_grid(p.B)), dim3(64 * kPolarChanWaves), 0, s, p);
+    return hipGetLastError();
+}
+
+}  // namespace bchk

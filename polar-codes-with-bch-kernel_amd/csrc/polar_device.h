@@ -146,6 +146,54 @@ inline uint32_t polar_mixed_lds_bytes(int U, int L, int K, int ssize, int csize,
     return (b + 15u) & ~15u;
 }
 
+// ---- the simulation front-end (polar_channel.hip): encoder, AWGN LLRs, error counters.
+// The encoder's tables (device pointers into the context's blob): u is built from the
+// information bits (inforank), the dynamic freezing constraints in symbol order (static ones
+// are zeros), then the layers' transform, innermost first, and the transmitted symbols.
+struct PolarEncTables {
+    const int16_t *inforank;  // [U] index of the symbol among the unfrozen ones, -1 = frozen
+    const int16_t *cwpos;     // [N] transmitted symbols
+    const uint64_t *krows;    // [nl][kPolarMaxKernel]
+    const uint32_t *dynoff;   // [ndyn + 1] first term of dynamic constraint d in dynterm
+    const uint16_t *dynterm;  // terms, ascending, the frozen symbol last
+    int32_t ndyn, nl, U, N, K;
+    int32_t ksize[kPolarMaxLayers];
+};
+// One launch over B words: an encode (info_in -> cw) or, with gen set, words
+// [word0, word0 + B) of the counter-based stream (bchk_philox.h): information bits, codeword,
+// LLR = (float)(-2 y / var), y = BPSK(bit 1 -> +1) + sigma z in double.
+struct PolarGenParams {
+    PolarEncTables t;
+    const uint8_t *info_in;  // [B][K] (encode)
+    uint8_t *info;           // [B][K] (generate; may be null)
+    uint8_t *cw;             // [B][N] (may be null when generating)
+    float *llr;              // [B][N] (generate)
+    uint64_t word0;
+    uint32_t B;
+    uint32_t seed_lo, seed_hi;
+    int32_t gen;
+    double sigma, var;
+};
+// CSimulator::Iterate's counters of one decoded batch (Simulator.cpp:201-318), added into
+// out8: words, block errors, information bit errors, code bit errors, ML errors, list errors,
+// raw bit errors, words with count <= 0.
+struct PolarCountParams {
+    const uint8_t *info_tx, *cw_tx;  // [B][K], [B][N] sent
+    const float *llr;                // [B][N]
+    const uint8_t *info, *cw;        // [B][L][K], [B][L][N] decoded lists
+    const int32_t *count;            // [B]
+    unsigned long long *out8;
+    uint8_t *flags;                  // [B] bit 0 block, 1 ML, 2 list error (may be null)
+    uint32_t B;
+    int32_t N, K, L;
+};
+constexpr int kPolarChanWaves = 4;  // waves per workgroup of both kernels, one word per wave
+// LDS bytes of one wave of the generate / encode kernel: the packed information bits (whole
+// 128-bit generator blocks) and two packed buffers of u (the layers ping-pong)
+constexpr uint32_t polar_gen_wave_bytes(int U, int K) {
+    return 8u * (uint32_t)(2 * ((K + 127) / 128) + 2) + 16u * (uint32_t)((U + 63) / 64);
+}
+
 // Packed partial sums of the all-Arikan kernel (polar_sclist.hip): per path C_0 (U bits,
 // the codeword) then C_λ (U >> (λ-1) bits, λ = 1..n), each starting on a 32-bit word; the
 // path stride is odd, so the same word of different paths falls in different banks. Writes

@@ -3,11 +3,15 @@
 // device tables and the batched launch. Replaces CMixedKernelListDecoder(Spec, ListSize)
 // and Decode(pLLR, pInfVectorList, pCodewordList) (headers/external/MixedKernelListDecoder.h:
 // 27-39, out/external/MixedKernelListDecoder.cpp:9, :211-268) and CMixedKernelEncoder::Encode
-// (out/external/MixedKernelEncoder.cpp:142-177). All decoding runs on the GPU.
+// (out/external/MixedKernelEncoder.cpp:142-177). All decoding runs on the GPU. Also the
+// simulation front-end (polar_channel.hip): encode, AWGN words, the simulator's counters and
+// the Eb/N0 sweep of CSimulator (out/external/Simulator.cpp:104-110, :139-335).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cctype>
+#include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +30,8 @@ hipError_t launch_polar(const PolarParams &p, int grid, size_t lds, hipStream_t 
 const void *polar_kernel_ptr();
 hipError_t launch_polar_mixed(const PolarMixedParams &p, int grid, size_t lds, hipStream_t s);
 const void *polar_mixed_kernel_ptr();
+hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
+hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s);
 void set_last_error(const char *msg);  // bchk_host.cpp: the message bchk_last_error returns
 }  // namespace bchk
 
@@ -89,12 +95,18 @@ struct bchk_polar {
     std::vector<uint64_t> dfcorr;
     std::vector<std::vector<int>> fc;  // freezing constraints (terms, frozen symbol last)
     std::vector<int> decision;         // constraint of each symbol, -1 = unfrozen
-    uint8_t *d_tab = nullptr;          // one blob: symmap | phase | cwpos | dfcorr
+    uint8_t *d_tab = nullptr;          // one blob: symmap | phase | cwpos | dfcorr | ... | encoder tables
     size_t off_symmap = 0, off_phase = 0, off_cwpos = 0, off_dfcorr = 0;
+    // the device encoder's tables (polar_device.h PolarEncTables)
+    std::vector<int16_t> inforank;
+    std::vector<uint32_t> dynoff;
+    std::vector<uint16_t> dynterm;
+    size_t off_inforank = 0, off_dynoff = 0, off_dynterm = 0;
     hipStream_t stream = nullptr;
     size_t lds = 0;
     int grid = 0;
     PBuf llr, info, cw, metric, count;
+    PBuf txinfo, txcw, flags, cnt8;  // bchk_polar_sweep_device's sent words, error flags, counters
     // time-budgeted launches of codes with search layers (PolarMixedParams::budget)
     PBuf rstate, rsave, unfinished;
     uint64_t budget_ticks = 0;  // 100 MHz ticks per launch, 0 = one launch per call
@@ -348,6 +360,20 @@ int parse_spec(bchk_polar *c, const char *spec, const char *kdir) {
         c->frozen[i] = c->decision[i] >= 0;
         if (c->decision[i] < 0) c->infopos.push_back((int16_t)i);
     }
+    // the device encoder: where each information bit goes, and the dynamic constraints (more
+    // than one term) in the order of their frozen symbols
+    c->inforank.assign(U, -1);
+    c->dynoff.assign(1, 0u);
+    c->dynterm.clear();
+    for (int i = 0, k = 0; i < U; ++i) {
+        const int ci = c->decision[i];
+        if (ci < 0) {
+            c->inforank[i] = (int16_t)k++;
+        } else if (c->fc[ci].size() > 1) {
+            for (int t : c->fc[ci]) c->dynterm.push_back((uint16_t)t);
+            c->dynoff.push_back((uint32_t)c->dynterm.size());
+        }
+    }
     return 0;
 }
 
@@ -458,6 +484,9 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     c->off_tent = o; o = al(o + 4 * c->tent.size());
     c->off_tbase = o; o = al(o + 4 * c->tbase.size());
     c->off_tlog = o; o = al(o + c->tlog.size());
+    c->off_inforank = o; o = al(o + 2 * (size_t)c->U);
+    c->off_dynoff = o; o = al(o + 4 * c->dynoff.size());
+    c->off_dynterm = o; o = al(o + 2 * c->dynterm.size() + 2);
     std::vector<uint8_t> blob(o, 0);
     memcpy(blob.data() + c->off_symmap, c->symmap.data(), 2 * (size_t)c->U);
     {
@@ -472,6 +501,9 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     if (!c->tent.empty()) memcpy(blob.data() + c->off_tent, c->tent.data(), 4 * c->tent.size());
     if (!c->tbase.empty()) memcpy(blob.data() + c->off_tbase, c->tbase.data(), 4 * c->tbase.size());
     if (!c->tlog.empty()) memcpy(blob.data() + c->off_tlog, c->tlog.data(), c->tlog.size());
+    memcpy(blob.data() + c->off_inforank, c->inforank.data(), 2 * (size_t)c->U);
+    memcpy(blob.data() + c->off_dynoff, c->dynoff.data(), 4 * c->dynoff.size());
+    if (!c->dynterm.empty()) memcpy(blob.data() + c->off_dynterm, c->dynterm.data(), 2 * c->dynterm.size());
     if (hipMalloc(&c->d_tab, o) != hipSuccess ||
         hipMemcpy(c->d_tab, blob.data(), o, hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -511,6 +543,10 @@ void bchk_polar_destroy(bchk_polar *c) {
     c->rstate.release();
     c->rsave.release();
     c->unfinished.release();
+    c->txinfo.release();
+    c->txcw.release();
+    c->flags.release();
+    c->cnt8.release();
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -693,6 +729,173 @@ int bchk_polar_encode_host(const bchk_polar *c, const uint8_t *info, size_t B, u
         }
         for (int i = 0; i < c->N; ++i) cw[b * c->N + i] = u[c->cwpos[i]];
     }
+    return 0;
+}
+
+}  // extern "C"
+
+namespace {
+
+PolarEncTables enc_tables(const bchk_polar *c) {
+    PolarEncTables t{};
+    t.inforank = reinterpret_cast<const int16_t *>(c->d_tab + c->off_inforank);
+    t.cwpos = reinterpret_cast<const int16_t *>(c->d_tab + c->off_cwpos);
+    t.krows = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_krows);
+    t.dynoff = reinterpret_cast<const uint32_t *>(c->d_tab + c->off_dynoff);
+    t.dynterm = reinterpret_cast<const uint16_t *>(c->d_tab + c->off_dynterm);
+    t.ndyn = (int32_t)c->dynoff.size() - 1;
+    t.nl = c->n;
+    t.U = c->U;
+    t.N = c->N;
+    t.K = c->K;
+    for (int j = 0; j < c->n; ++j) t.ksize[j] = c->ksize[j];
+    return t;
+}
+
+// the first `need` set bits 0 of flags[0, nb): the words up to and including the one that
+// carries the need-th block error (nb when there are fewer)
+size_t cut_at_error(const std::vector<uint8_t> &flags, size_t nb, uint64_t need) {
+    for (size_t w = 0; w < nb; ++w)
+        if ((flags[w] & 1u) && --need == 0) return w + 1;
+    return nb;
+}
+
+}  // namespace
+
+extern "C" {
+
+// CMixedKernelEncoder::Encode (MixedKernelEncoder.cpp:142-177) on the device
+// (polar_channel.hip), bit for bit bchk_polar_encode_host.
+int bchk_polar_encode_device(bchk_polar *c, const uint8_t *d_info, size_t B, uint8_t *d_cw, void *stream) {
+    if (!c || (B && ((c->K && !d_info) || !d_cw))) return pfail(BCHK_EINVAL, "NULL argument");
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    if (B == 0) return 0;
+    PolarGenParams p{};
+    p.t = enc_tables(c);
+    p.info_in = d_info;
+    p.cw = d_cw;
+    p.B = (uint32_t)B;
+    PHIP_TRY(launch_polar_gen(p, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
+
+// Words [word0, word0 + B) of the counter-based stream `seed` at Eb/N0 snr_db: the noise
+// deviation of CSimulator::SetEbN0 (Simulator.cpp:108, N the transmitted length).
+int bchk_polar_generate_device(bchk_polar *c, double snr_db, size_t B, uint64_t seed, uint64_t word0,
+                               uint8_t *d_info, uint8_t *d_cw, float *d_llr, void *stream) {
+    if (!c || (B && !d_llr)) return pfail(BCHK_EINVAL, "NULL argument");
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    if (B == 0) return 0;
+    if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
+    PolarGenParams p{};
+    p.t = enc_tables(c);
+    p.info = d_info;
+    p.cw = d_cw;
+    p.llr = d_llr;
+    p.word0 = word0;
+    p.B = (uint32_t)B;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    p.gen = 1;
+    p.sigma = sqrt(0.5 * pow(10, -snr_db / 10) * c->N / c->K);
+    p.var = p.sigma * p.sigma;  // CModem::SetNoiseVariance (Simulator.cpp:109)
+    PHIP_TRY(launch_polar_gen(p, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
+
+int bchk_polar_count_device(bchk_polar *c, const uint8_t *d_info_tx, const uint8_t *d_cw_tx, const float *d_llr,
+                            const uint8_t *d_info, const uint8_t *d_cw, const int32_t *d_count, size_t B,
+                            uint64_t *d_out8, uint8_t *d_flags, void *stream) {
+    if (!c || (B && ((c->K && (!d_info_tx || !d_info)) || !d_cw_tx || !d_llr || !d_cw || !d_count || !d_out8)))
+        return pfail(BCHK_EINVAL, "NULL argument");
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    if (B == 0) return 0;
+    PolarCountParams p{};
+    p.info_tx = d_info_tx;
+    p.cw_tx = d_cw_tx;
+    p.llr = d_llr;
+    p.info = d_info;
+    p.cw = d_cw;
+    p.count = d_count;
+    p.out8 = reinterpret_cast<unsigned long long *>(d_out8);
+    p.flags = d_flags;
+    p.B = (uint32_t)B;
+    p.N = c->N;
+    p.K = c->K;
+    p.L = c->L;
+    PHIP_TRY(launch_polar_count(p, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
+
+// The AWGN/BPSK simulation loop (CSimulator::Iterate over a range of Eb/N0) end to end on the
+// device: per point, batches are generated, decoded and counted until max_words words or
+// max_errors block errors. The batch that reaches max_errors is cut in word order from its
+// per-word flags and its prefix counted again (the decoded lists are still in the buffers),
+// and the next point starts at the word after the cut: the records depend on the arguments
+// only, not on `batch`.
+int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int points, uint64_t max_words,
+                            uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
+                            double *seconds, uint64_t *words_decoded) {
+    if (!c || !out) return pfail(BCHK_EINVAL, "NULL argument");
+    if (points <= 0 || max_words == 0 || max_errors == 0)
+        return pfail(BCHK_EINVAL, "points, max_words and max_errors must be positive");
+    const size_t N = (size_t)c->N, K = (size_t)std::max(c->K, 1), L = (size_t)c->L;
+    const size_t per_word = 4 * N + L * (K + N) + 4 * L + 4 + K + N + 1;
+    size_t Bm = batch;
+    if (!Bm) {  // a few waves of the decoder's persistent grid, within 1 GiB of buffers
+        Bm = std::max<size_t>(4096, 16 * (size_t)c->grid);
+        Bm = std::max<size_t>(1, std::min(Bm, (size_t(1) << 30) / per_word));
+    }
+    Bm = (size_t)std::min<uint64_t>(std::min<uint64_t>(Bm, max_words), 0xFFFFFFFFull);
+    int rc;
+    if ((rc = c->llr.ensure(Bm * N * sizeof(float))) || (rc = c->info.ensure(Bm * L * K)) ||
+        (rc = c->cw.ensure(Bm * L * N)) || (rc = c->metric.ensure(Bm * L * sizeof(float))) ||
+        (rc = c->count.ensure(Bm * sizeof(int32_t))) || (rc = c->txinfo.ensure(Bm * K)) ||
+        (rc = c->txcw.ensure(Bm * N)) || (rc = c->flags.ensure(Bm)) || (rc = c->cnt8.ensure(8 * sizeof(uint64_t))))
+        return rc;
+    const hipStream_t s = c->stream;
+    uint64_t *d8 = (uint64_t *)c->cnt8.p;
+    std::vector<uint8_t> flags;
+    const auto t0 = std::chrono::steady_clock::now();
+    uint64_t word = 0, decoded = 0;
+    for (int pt = 0; pt < points; ++pt) {
+        bchk_polar_point &r = out[pt];
+        r.snr_db = snr_from + pt * snr_step;
+        for (uint64_t &v : r.c) v = 0;
+        while (r.c[0] < max_words && r.c[1] < max_errors) {
+            const size_t nb = (size_t)std::min<uint64_t>(Bm, max_words - r.c[0]);
+            uint64_t h[8];
+            if ((rc = bchk_polar_generate_device(c, r.snr_db, nb, seed, word, (uint8_t *)c->txinfo.p,
+                                                 (uint8_t *)c->txcw.p, (float *)c->llr.p, s)) ||
+                (rc = bchk_polar_decode_device(c, (const float *)c->llr.p, nb, (uint8_t *)c->info.p, (uint8_t *)c->cw.p,
+                                               (float *)c->metric.p, (int32_t *)c->count.p, s)))
+                return rc;
+            decoded += nb;
+            size_t used = nb;
+            for (int pass = 0; pass < 2; ++pass) {  // the whole batch, then its prefix up to the cut
+                PHIP_TRY(hipMemsetAsync(d8, 0, 8 * sizeof(uint64_t), s));
+                if ((rc = bchk_polar_count_device(c, (const uint8_t *)c->txinfo.p, (const uint8_t *)c->txcw.p,
+                                                  (const float *)c->llr.p, (const uint8_t *)c->info.p,
+                                                  (const uint8_t *)c->cw.p, (const int32_t *)c->count.p, used, d8,
+                                                  pass ? nullptr : (uint8_t *)c->flags.p, s)))
+                    return rc;
+                PHIP_TRY(hipMemcpyAsync(h, d8, sizeof h, hipMemcpyDeviceToHost, s));
+                PHIP_TRY(hipStreamSynchronize(s));
+                if (h[0] != used)
+                    return pfail(BCHK_EHIP, "counters saw %llu of %zu words", (unsigned long long)h[0], used);
+                if (pass || r.c[1] + h[1] < max_errors) break;
+                flags.resize(nb);
+                PHIP_TRY(hipMemcpyAsync(flags.data(), c->flags.p, nb, hipMemcpyDeviceToHost, s));
+                PHIP_TRY(hipStreamSynchronize(s));
+                used = cut_at_error(flags, nb, max_errors - r.c[1]);
+                if (used == nb) break;
+            }
+            for (int q = 0; q < 8; ++q) r.c[q] += h[q];
+            word += used;
+        }
+    }
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    if (words_decoded) *words_decoded = decoded;
     return 0;
 }
 

@@ -9,6 +9,14 @@ information/codeword rows + 4L metrics + 4 count written) against the 8 TB/s roo
 the best path, and the oracle (oracle/polar_oracle.c, one host core) on a bounded sample.
 
     python scripts/bench_polar.py --n 10 --K 512 --L 8 --snr 2.0 --batch 65536
+
+--sim times the whole simulation instead (bchk_polar_sweep_device: words generated, decoded and
+counted on the GPU, one Eb/N0 point cut by words) in words/s of wall time, at (1024, 512) and
+(64, 32) with L = 8, beside the decode-only rate of the same context in the same run (device
+events around bchk_polar_decode_device over LLRs from bchk_polar_generate_device). One JSON
+line per shape.
+
+    python scripts/bench_polar.py --sim --snr 2.0
 """
 import argparse
 import json
@@ -25,8 +33,62 @@ sys.path.insert(0, REPO)
 HBM_PEAK_GBS = 8000.0
 
 
+SIM_SHAPES = ((10, 512, 8), (6, 32, 8))  # n, K, L
+
+
+def sim(a):
+    import torch
+    from bchk_pkg import load
+    from polar_lib import arikan_spec
+
+    dev = torch.device("cuda:0")
+    for n, K, L in SIM_SHAPES:
+        d = load().PolarListDecoder(arikan_spec(n, K, dyn=a.dyn, seed=1), L)
+        N = d.N
+        B = a.sim_batch or (1 << 14 if n >= 10 else 1 << 18)
+        t_llr = torch.zeros((B, N), dtype=torch.float32, device=dev)
+        t_info = torch.zeros((B, L, K), dtype=torch.uint8, device=dev)
+        t_cw = torch.zeros((B, L, N), dtype=torch.uint8, device=dev)
+        t_met = torch.zeros((B, L), dtype=torch.float32, device=dev)
+        t_cnt = torch.zeros(B, dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        d.generate_device(a.snr, B, t_llr.data_ptr(), seed=1)
+        st = torch.cuda.ExternalStream(d.stream)
+
+        def run():
+            d.decode_device(t_llr.data_ptr(), B, t_info.data_ptr(), t_cw.data_ptr(), t_met.data_ptr(),
+                            t_cnt.data_ptr())
+
+        for _ in range(a.warmup):
+            run()
+        d.sync()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(st)
+        for _ in range(a.steps):
+            run()
+        e1.record(st)
+        d.sync()
+        decode_cps = B * a.steps / (e0.elapsed_time(e1) * 1e-3)
+        # the sweep: the same words (stream 1 from word 0), `steps` batches, never cut by errors
+        words = B * a.steps
+        d.sweep_device(a.snr, 0.0, 1, B, 1 << 62, seed=1, batch=B)  # warm-up: buffers, code objects
+        recs, secs, done = d.sweep_device(a.snr, 0.0, 1, words, 1 << 62, seed=1, batch=B)
+        c = recs[0][1]
+        assert done == words and c[0] == words
+        print(json.dumps({
+            "metric": "polar simulation words/s", "value": done / secs, "unit": "words/s",
+            "config": {"workload": f"Arikan polar ({N},{K}) dyn={a.dyn}, L={L}, Eb/N0={a.snr} dB", "batch": B,
+                       "words": words},
+            "sweep_seconds": secs, "decode_only_codewords_per_s": decode_cps,
+            "sweep_over_decode_only": (done / secs) / decode_cps,
+            "counters": dict(zip(load().POLAR_COUNTERS, c)), "fer": c[1] / c[0]}), flush=True)
+        d.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sim", action="store_true", help="time sweep_device end to end at the two standard shapes")
+    ap.add_argument("--sim-batch", type=int, default=0, help="words per batch of --sim (0: 2^14 / 2^18)")
     ap.add_argument("--n", type=int, default=10)
     ap.add_argument("--K", type=int, default=512)
     ap.add_argument("--L", type=int, default=8)
@@ -38,6 +100,8 @@ def main():
     ap.add_argument("--no-cw", action="store_true", help="do not write the codeword rows")
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
     a = ap.parse_args()
+    if a.sim:
+        return sim(a)
 
     import torch
     from bchk_pkg import load
