@@ -406,6 +406,60 @@ int bchk_kernel_column_search(int power, const uint8_t *K, const float *llr, int
                               uint64_t *rng_state, int device, uint8_t *best, uint32_t *perm,
                               uint64_t *best_sum, uint64_t *best_cmp, int64_t *best_index);
 
+/* ---- BEC polarisation behaviour of a kernel and the code design built on it
+ * (csrc/kernel_bec.hip, csrc/polar_design.cpp). The decoder's conventions: c = sum_i u_i row_i,
+ * phase i is decoded knowing u_0..u_{i-1}. With the columns of E erased and S kept, phase i is
+ * uncorrectable iff row_i|S lies in the span of {row_j|S : j > i}. K must be invertible
+ * (BCHK_EINVAL otherwise, as for a kernel file). */
+/* The primitive: per erasure pattern (bit j = column j erased; bits >= l ignored) the mask of
+ * uncorrectable phases (bit i = phase i). 2 <= l <= 64. */
+int bchk_kernel_bec_masks(const uint8_t *K, int l, const uint64_t *patterns, size_t n, int device,
+                          uint64_t *masks);
+/* Exact polarisation behaviour, 2 <= l <= 32: counts[i * (l + 1) + w] = the erasure patterns
+ * of weight w that leave phase i uncorrectable, all C(l, w) of them enumerated for every
+ * 0 <= w_lo <= w <= w_hi <= l (other weights are left 0). This is the table of the
+ * reference's CBECCapacityEvaluator (out/external/CapacityEvaluator.cpp:100-140). The
+ * enumeration is cut into kernel launches of at most 2^28 patterns. */
+int bchk_kernel_bec_behaviour(const uint8_t *K, int l, int w_lo, int w_hi, int device, uint64_t *counts);
+/* The same for any 2 <= l <= 64 with at most `samples` (1..2^40) patterns per weight: a weight
+ * with C(l, w) <= samples is enumerated (exact[w] = 1, tried[w] = C(l, w)); any other takes
+ * `samples` uniform w-subsets (exact[w] = 0, tried[w] = samples), sample s of weight w being
+ * the subset of colex rank r, r uniform below C(l, w) from the Philox4x32-10 stream keyed by
+ * seed at counters (s low, s high, w, 0xBEC00000 + attempt) -- a function of (seed, w, s)
+ * only, so the result does not depend on how the work is cut into lanes and launches
+ * (BCHK_BEC_RUN in the environment = patterns per lane, 1..4095; default sized from the
+ * launch). unc[i * (l + 1) + w] = uncorrectable patterns among the tried ones; the estimate
+ * of counts is unc C(l, w) / tried. patterns (may be NULL) receives the tried[pattern_weight]
+ * patterns of weight pattern_weight, in rank / sample order (room for min(C(l, w), samples)). */
+int bchk_kernel_bec_sample(const uint8_t *K, int l, uint64_t samples, uint64_t seed, int device, uint64_t *unc,
+                           uint64_t *tried, uint8_t *exact, int pattern_weight, uint64_t *patterns);
+/* CBECCapacityEvaluator::GetSubchannelCapacity (CapacityEvaluator.cpp:124-140) restated
+ * (the reference's evaluator is never built: parity unpinned): the capacity of phase `phase`
+ * over a BEC of capacity C, 1 - sum_w counts[phase][w] P^w C^(l - w) with P = 1 - C, by the
+ * same Horner rule in double; 1 - counts[phase][l] at C = 0. Host only. */
+int bchk_kernel_bec_capacity(const uint64_t *counts, int l, int phase, double C, double *out);
+/* A kernel file in the reference's format (Kernel.cpp:93-134): the size, the matrix and, when
+ * counts is given, the BEC section CBECCapacityEvaluator's constructor parses -- channel id 3
+ * (ec_BEC, headers/external/Simulator.h:13-17) and l rows "0 counts[i][1] .. counts[i][l]".
+ * bchk_polar_create_kdir reads such files (it ignores what follows the matrix). Host only. */
+int bchk_kernel_write_file(const char *path, const uint8_t *K, int l, const uint64_t *counts);
+/* BEC design of a polar code over mixed kernels: `layers` is the specification's kernel-name
+ * line ("-e16.txt A A"; files relative to kdir), K the dimension, capacity the design BEC
+ * capacity. A matrix layer's table is the BEC section of its file when there is one;
+ * otherwise it is computed on the GPU (bchk_kernel_bec_behaviour up to size 32,
+ * bchk_kernel_bec_sample with (samples, seed) above), so all-Arikan designs and files with
+ * tables need no device. Symbol i has mixed-radix digits (a_0 .. a_{n-1}), a_0 most
+ * significant; layer 0 faces the channel (MixedKernelEncoder.cpp:161-173), so its capacity is
+ * T_{n-1,a_{n-1}}( .. T_{1,a_1}(T_{0,a_0}(capacity))), T of an "A" layer being C^2 and
+ * 2C - C^2 (Kernel.cpp:70-75). The K largest capacities carry information, ties going to
+ * the higher index. cap (may be NULL) receives the U capacities; spec receives the text
+ * "U K 0 n 0 0", the layer line and "1 f" per frozen symbol, ascending (no shortening,
+ * puncturing or dynamic freezing). *needed = the bytes the text takes with its terminator
+ * (0 when the arguments were rejected before it was formed); a buffer shorter than that is
+ * BCHK_EINVAL. */
+int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double capacity, uint64_t samples,
+                          uint64_t seed, int device, double *cap, char *spec, size_t spec_len, size_t *needed);
+
 const char *bchk_last_error(void);
 const char *bchk_version(void);
 

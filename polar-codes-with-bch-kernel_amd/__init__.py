@@ -42,7 +42,9 @@ EXPORTS = (
     "bchk_polar_scratch_bytes", "bchk_polar_encode_device", "bchk_polar_generate_device",
     "bchk_polar_count_device", "bchk_polar_sweep_device",
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
-    "bchk_kernel_column_search", "bchk_last_error", "bchk_version",
+    "bchk_kernel_column_search",
+    "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
+    "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_last_error", "bchk_version",
 )
 
 # struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device
@@ -151,6 +153,13 @@ def lib():
     L.bchk_kernel_column_costs.argtypes = [i32, vp, vp, i32, vp, vp]
     L.bchk_kernel_column_search.argtypes = [i32, vp, vp, i32, u64, C.POINTER(u64), i32, vp, vp,
                                             C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_int64)]
+    L.bchk_kernel_bec_masks.argtypes = [vp, i32, vp, sz, i32, vp]
+    L.bchk_kernel_bec_behaviour.argtypes = [vp, i32, i32, i32, i32, vp]
+    L.bchk_kernel_bec_sample.argtypes = [vp, i32, u64, u64, i32, vp, vp, vp, i32, vp]
+    L.bchk_kernel_bec_capacity.argtypes = [vp, i32, i32, dbl, C.POINTER(dbl)]
+    L.bchk_kernel_write_file.argtypes = [C.c_char_p, vp, i32, vp]
+    L.bchk_polar_design_bec.argtypes = [C.c_char_p, C.c_char_p, i32, dbl, u64, u64, i32, vp, C.c_char_p, sz,
+                                        C.POINTER(sz)]
     L.bchk_last_error.restype = C.c_char_p
     L.bchk_version.restype = C.c_char_p
     _lib = L
@@ -587,6 +596,79 @@ def kernel_column_search(power, K, llr, mode=KSEARCH_EXHAUSTIVE, count=0, rng_st
     _check(lib().bchk_kernel_column_search(power, _p(K), _p(y), mode, count, C.byref(st), device,
                                            _p(best), _p(perm), C.byref(s), C.byref(c), C.byref(i)))
     return dict(best=best, perm=perm, sum=s.value, cmp=c.value, index=i.value, rng_state=st.value)
+
+
+def kernel_bec_masks(K, patterns, device=0):
+    """Per erasure pattern (uint64, bit j = column j erased) the mask of uncorrectable phases
+    (bit i = phase i) of the invertible kernel K (2 <= l <= 64), computed on the GPU."""
+    K = np.ascontiguousarray(K, np.uint8)
+    pat = np.ascontiguousarray(patterns, np.uint64)
+    masks = np.zeros(pat.shape[0], np.uint64)
+    _check(lib().bchk_kernel_bec_masks(_p(K), K.shape[0], _p(pat), pat.shape[0], device, _p(masks)))
+    return masks
+
+
+def kernel_bec_behaviour(K, w_lo=0, w_hi=None, device=0):
+    """Exact BEC polarisation behaviour of K (l <= 32): counts [l][l + 1] uint64, counts[i][w] =
+    the weight-w erasure patterns that leave phase i uncorrectable, for w_lo <= w <= w_hi
+    (default: every weight), enumerated on the GPU."""
+    K = np.ascontiguousarray(K, np.uint8)
+    l = K.shape[0]
+    counts = np.zeros((l, l + 1), np.uint64)
+    _check(lib().bchk_kernel_bec_behaviour(_p(K), l, w_lo, l if w_hi is None else w_hi, device, _p(counts)))
+    return counts
+
+
+def kernel_bec_sample(K, samples, seed=1, device=0, pattern_weight=None):
+    """The same for l <= 64 with at most `samples` patterns per weight -> (unc [l][l + 1], tried
+    [l + 1], exact [l + 1] bool): weights with C(l, w) <= samples enumerated, the others sampled
+    from the Philox stream `seed`; counts[i][w] is estimated by unc C(l, w) / tried. With
+    pattern_weight, also the patterns tried at that weight (uint64)."""
+    K = np.ascontiguousarray(K, np.uint8)
+    l = K.shape[0]
+    unc = np.zeros((l, l + 1), np.uint64)
+    tried = np.zeros(l + 1, np.uint64)
+    exact = np.zeros(l + 1, np.uint8)
+    pat = None if pattern_weight is None else np.zeros(samples, np.uint64)
+    _check(lib().bchk_kernel_bec_sample(_p(K), l, samples, seed, device, _p(unc), _p(tried), _p(exact),
+                                        0 if pat is None else pattern_weight, None if pat is None else _p(pat)))
+    if pat is None:
+        return unc, tried, exact.astype(bool)
+    return unc, tried, exact.astype(bool), pat[:int(tried[pattern_weight])]
+
+
+def kernel_bec_capacity(counts, phase, capacity):
+    """CBECCapacityEvaluator::GetSubchannelCapacity: the capacity of `phase` of the kernel with
+    BEC table counts [l][l + 1] over a BEC of the given capacity (host only)."""
+    counts = np.ascontiguousarray(counts, np.uint64)
+    out = C.c_double()
+    _check(lib().bchk_kernel_bec_capacity(_p(counts), counts.shape[0], phase, capacity, C.byref(out)))
+    return out.value
+
+
+def write_kernel_file(path, K, counts=None):
+    """A kernel file in the reference's format: size, matrix and, with counts [l][l + 1], the BEC
+    section (channel id 3) its capacity evaluator parses."""
+    K = np.ascontiguousarray(K, np.uint8)
+    if counts is not None:
+        counts = np.ascontiguousarray(counts, np.uint64)
+        if counts.shape != (K.shape[0], K.shape[0] + 1):
+            raise BchkError("counts must be [l][l + 1]")
+    _check(lib().bchk_kernel_write_file(os.fsencode(path), _p(K), K.shape[0], None if counts is None else _p(counts)))
+
+
+def design_bec(layers, K, capacity=0.5, kernel_dir=None, samples=1 << 16, seed=1, device=0):
+    """BEC design of a polar code over the kernels of `layers` (names, or the spec's layer line):
+    -> (spec text for PolarListDecoder, capacities [U] of the symbols). Matrix kernels take
+    their BEC table from their file, or from the GPU when the file has none."""
+    line = layers if isinstance(layers, str) else " ".join(layers)
+    cap = np.zeros(16384, np.float64)
+    buf = C.create_string_buffer(64 + len(line) + 8 * 16384)
+    needed = C.c_size_t()
+    _check(lib().bchk_polar_design_bec(line.encode(), kernel_dir.encode() if kernel_dir else None, K, capacity,
+                                       samples, seed, device, _p(cap), buf, len(buf), C.byref(needed)))
+    spec = buf.value.decode()
+    return spec, cap[:int(spec.split()[0])].copy()
 
 
 def version():
