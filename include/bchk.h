@@ -181,7 +181,14 @@ int bchk_sweep(bchk_ctx *ctx, long p, long e, double max_snr, uint64_t *rng_stat
 /* On-GPU channel front-end (the encode + AWGN step of src/bchCoder.cpp:120-132,243-250 as a
  * batched kernel): words [word0, word0 + B) of a counter-based stream (Philox4x32-10 keyed
  * by seed; word w depends only on (seed, w)) at Eb/N0 snr_db -- uniform information bits,
- * c(x) = info(x) g(x), y = BPSK(c) + N(0, sd) with sd as src/dataForPlot.cpp:45. The same
+ * c(x) = info(x) g(x), y = BPSK(c) + N(0, sd) with sd as src/dataForPlot.cpp:45.
+ * Coefficient i of info(x) is bit (i % 128) & 31 of output word (i % 128) >> 5 of counter
+ * (w low, w high, 0xFFFFFFFF, 128 (i / 128)): counter word 3 is the BIT OFFSET of the 128-bit
+ * block here, where the polar stream (bchk_polar_generate_device) passes the block INDEX; the
+ * two streams never share a counter and both are kept as they are. The noise of flat element
+ * G = w n + position is element G & 1 of the Box-Muller pair (sqrt(-2 ln u1) cos 2 pi u2, ...
+ * sin 2 pi u2) of counter (G / 2 low, G / 2 high, 0x5EED, 0), u = (a 2^21 + (b >> 11) + 1)
+ * 2^-53 from output words (a, b) = (0, 1) for u1 and (2, 3) for u2. The same
  * distribution as the reference's words, NOT its minstd_rand0 stream (bchk_generate_host is
  * the bit-exact one). d_tx [B][n] u8, d_y [B][n] f64 on device. */
 int bchk_generate_device(bchk_ctx *ctx, double snr_db, size_t B, uint64_t seed, uint64_t word0,

@@ -1,10 +1,20 @@
 // bchk_philox.h -- the counter-based generator of the on-GPU channel front-ends
-// (bchk_channel.hip for BCH words, polar_channel.hip for polar words). Device code only.
+// (bchk_channel.hip for BCH words, polar_channel.hip for polar words) and of the sampled BEC
+// design (kernel_bec.hip). Device code only.
 //
 // Counter layout of a (seed, word) stream, keyed by (seed low, seed high):
-//   information bits of word w, 128 at a time:  (w low, w high, 0xFFFFFFFF, block)
-//   noise of flat element G = w * n + position: one of the Box-Muller pair of counter
-//                                               (G / 2 low, G / 2 high, 0x5EED, 0)
+//   information bits of word w, 128 at a time:  (w low, w high, 0xFFFFFFFF, c3); bit q of the
+//                                               block is bit q & 31 of output word q >> 5.
+//       BCH stream (chan_kernel):               c3 = the bit offset of the block (0, 128)
+//       polar stream (polar_gen_kernel):        c3 = the index of the block (0, 1, 2, ...)
+//     The two differ from the second block on (only BCH(255,139) has one among the built-in
+//     BCH codes). Both stay as they are: recorded profiles were produced with them, and the
+//     two streams never share a counter, so neither is wrong -- only different.
+//   noise of flat element G = w * n + position: element G & 1 of the Box-Muller pair of counter
+//                                               (G / 2 low, G / 2 high, 0x5EED, 0): u1 from
+//                                               output words (0, 1), u2 from (2, 3)
+//   BEC pattern draw of sample s, weight w:     (s low, s high, w, 0xBEC00000 + attempt)
+// tests/philox_lib.py restates all of it; tests/test_stream_reference.py compares.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
