@@ -467,6 +467,49 @@ int bchk_kernel_write_file(const char *path, const uint8_t *K, int l, const uint
 int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double capacity, uint64_t samples,
                           uint64_t seed, int device, double *cap, char *spec, size_t spec_len, size_t *needed);
 
+/* ---- Genie-aided SC and the Monte-Carlo AWGN design built on it (csrc/polar_genie.hip,
+ * csrc/polar_host.cpp, csrc/polar_design.cpp). Symbol phi of a word is decoded by one SC path
+ * with the TRUE u_0..u_{phi-1} (the encoder's inputs, rebuilt from the sent information bits as
+ * bchk_polar_generate_device's encoder forms them) fed back: LLR_phi is, bit for bit, the value
+ * bchk_polar_decode_device computes for a path whose earlier decisions were u_0..u_{phi-1}
+ * (LoadLLRs with 100000 at shortened and 0 at punctured symbols, f/g on Arikan layers, coset
+ * enumeration or the trellis on matrix layers under the context's per-layer choice,
+ * BCHK_POLAR_TRELLIS). Per symbol phi = 0..U-1, frozen symbols included, and per word:
+ *   err[phi]  += 1 when (LLR_phi < 0 ? 1 : 0) != u_phi            (the decoder's decision rule)
+ *   soft[phi] += q, q = (int64) of c * 65536.0f rounded to nearest even, c = s clamped to
+ *                [-32768, 32768], s = u_phi ? -LLR_phi : LLR_phi   (the product is exact in float)
+ * The sums are integers: they do not depend on the grid, on how a range of words is split into
+ * calls or batches, or on the order of waves. A code with a search layer (a matrix kernel above
+ * 32, or BCHK_POLAR_ML on any layer) is BCHK_EINVAL; so is a length whose one-path state exceeds
+ * the 160 KiB LDS. Works for any list_size of the context. */
+/* One batch: d_info_tx [B][K] sent information bits, d_llr [B][N] channel LLRs; d_err and d_soft
+ * ([U] each, device) are ADDED into; d_dec_llr [B][U] float (the decision LLRs) and d_u [B][U]
+ * bytes (the rebuilt encoder inputs) may each be NULL -- the rows then go to scratch the context
+ * owns, grown (a device allocation) when a call needs more than any before it. Enqueues on
+ * `stream` (NULL = the context's stream); B = 0 is a no-op; B > 2^32 - 1 is BCHK_EINVAL. */
+int bchk_polar_genie_device(bchk_polar *pc, const uint8_t *d_info_tx, const float *d_llr, size_t B,
+                            uint64_t *d_err, int64_t *d_soft, float *d_dec_llr, uint8_t *d_u, void *stream);
+/* Words [word0, word0 + words) of bchk_polar_generate_device's stream `seed` at snr_db, in batches
+ * of at most `batch` words (0 = sized from the kernel's grid), into buffers the context owns:
+ * err and soft (host, [U] each) are overwritten with the sums, a function of (code, snr_db, seed,
+ * word0, words) only. Synchronous, on the context's stream. 1 <= words <= 2^31 (BCHK_EINVAL
+ * otherwise: |q| <= 2^31, so soft stays inside 64 bits); seconds (may be NULL) = wall time. */
+int bchk_polar_genie_run(bchk_polar *pc, double snr_db, uint64_t words, uint64_t seed, uint64_t word0,
+                         size_t batch, uint64_t *err, int64_t *soft, double *seconds);
+/* Monte-Carlo AWGN design over the kernels of `layers` (as bchk_polar_design_bec): the code
+ * "U K 0 n 0 0" with the lowest U - K indices frozen (the rate K / U fixes the noise deviation;
+ * the statistics do not depend on the frozen set) goes through bchk_polar_genie_run(snr_db,
+ * words, seed, word0 = 0, batch = 0) on `device`; symbol i is better than j when err_i < err_j,
+ * on a tie when soft_i > soft_j, on a further tie when i > j; the K best carry information. spec
+ * receives the text in bchk_polar_design_bec's format (frozen symbols ascending; no shortening,
+ * puncturing or dynamic freezing), err / soft (may be NULL) the U sums. 1 <= K <= U and
+ * 1 <= words <= 2^31, else BCHK_EINVAL with nothing written; *needed and spec_len as in
+ * bchk_polar_design_bec (a short buffer is BCHK_EINVAL with *needed set and nothing else
+ * written). */
+int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words,
+                            uint64_t seed, int device, uint64_t *err, int64_t *soft, char *spec, size_t spec_len,
+                            size_t *needed);
+
 const char *bchk_last_error(void);
 const char *bchk_version(void);
 

@@ -44,7 +44,8 @@ EXPORTS = (
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
     "bchk_kernel_column_search",
     "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
-    "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_last_error", "bchk_version",
+    "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_polar_genie_device", "bchk_polar_genie_run",
+    "bchk_polar_design_genie", "bchk_last_error", "bchk_version",
 )
 
 # struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device
@@ -160,6 +161,10 @@ def lib():
     L.bchk_kernel_write_file.argtypes = [C.c_char_p, vp, i32, vp]
     L.bchk_polar_design_bec.argtypes = [C.c_char_p, C.c_char_p, i32, dbl, u64, u64, i32, vp, C.c_char_p, sz,
                                         C.POINTER(sz)]
+    L.bchk_polar_genie_device.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bchk_polar_genie_run.argtypes = [vp, dbl, u64, u64, u64, sz, vp, vp, C.POINTER(dbl)]
+    L.bchk_polar_design_genie.argtypes = [C.c_char_p, C.c_char_p, i32, dbl, u64, u64, i32, vp, vp, C.c_char_p, sz,
+                                          C.POINTER(sz)]
     L.bchk_last_error.restype = C.c_char_p
     L.bchk_version.restype = C.c_char_p
     _lib = L
@@ -482,6 +487,24 @@ class PolarListDecoder:
                                              C.byref(words)))
         return [(float(r["snr_db"]), [int(v) for v in r["c"]]) for r in out], secs.value, words.value
 
+    def genie_device(self, d_info_tx, d_llr, B, d_err, d_soft, d_dec_llr=None, d_u=None, stream=None):
+        """Genie-aided SC of one batch (device pointers): symbol phi of every word decoded with the
+        true earlier symbols fed back. d_err (u64) and d_soft (i64), [U] each, are added into (the
+        definitions: include/bchk.h); d_dec_llr [B][U] f32 and d_u [B][U] u8, where given, receive
+        the decision LLRs and the rebuilt encoder inputs."""
+        _check(lib().bchk_polar_genie_device(self._h, d_info_tx or None, d_llr or None, B, d_err or None,
+                                             d_soft or None, d_dec_llr or None, d_u or None, stream))
+
+    def genie_run(self, snr_db, words, seed=1, word0=0, batch=0):
+        """Words [word0, word0 + words) of generate_device's stream through genie_device:
+        (err [U] u64, soft [U] i64, seconds), a function of (code, snr_db, seed, word0, words)."""
+        err = np.zeros(self.U, np.uint64)
+        soft = np.zeros(self.U, np.int64)
+        secs = C.c_double(0.0)
+        _check(lib().bchk_polar_genie_run(self._h, snr_db, words, seed, word0, batch, _p(err), _p(soft),
+                                          C.byref(secs)))
+        return err, soft, secs.value
+
     def sync(self):
         _check(lib().bchk_polar_sync(self._h))
 
@@ -669,6 +692,22 @@ def design_bec(layers, K, capacity=0.5, kernel_dir=None, samples=1 << 16, seed=1
                                        samples, seed, device, _p(cap), buf, len(buf), C.byref(needed)))
     spec = buf.value.decode()
     return spec, cap[:int(spec.split()[0])].copy()
+
+
+def design_genie(layers, K, snr_db, words, kernel_dir=None, seed=1, device=0):
+    """Monte-Carlo AWGN design over the kernels of `layers`: the symbols ranked by their genie-aided
+    error counts over `words` words of the stream `seed` at Eb/N0 snr_db (ties: the larger soft sum,
+    then the higher index) -> (spec text for PolarListDecoder, err [U] u64, soft [U] i64)."""
+    line = layers if isinstance(layers, str) else " ".join(layers)
+    err = np.zeros(16384, np.uint64)
+    soft = np.zeros(16384, np.int64)
+    buf = C.create_string_buffer(64 + len(line) + 8 * 16384)
+    needed = C.c_size_t()
+    _check(lib().bchk_polar_design_genie(line.encode(), kernel_dir.encode() if kernel_dir else None, K, snr_db, words,
+                                         seed, device, _p(err), _p(soft), buf, len(buf), C.byref(needed)))
+    spec = buf.value.decode()
+    U = int(spec.split()[0])
+    return spec, err[:U].copy(), soft[:U].copy()
 
 
 def version():

@@ -24,19 +24,14 @@
 
 #include "bchk_philox.h"
 #include "polar_device.h"
+#include "polar_enc_device.h"
 
 namespace bchk {
 
 namespace {
 
-// LDS written by some lanes of the wave is read by others after this
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ uint32_t ubit(const uint32_t *u, int pos) { return (u[pos >> 5] >> (pos & 31)) & 1u; }
+using penc::ubit;
+using penc::wave_sync;
 
 __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGenParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t psm[];
@@ -58,39 +53,16 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
                 ib[2 * blk + 1] = (uint64_t)r.z | ((uint64_t)r.w << 32);
             }
         } else {
-            const uint8_t *in = p.info_in + w * (uint64_t)K;
-            for (int g = 0; g * 64 < K; ++g) {
-                const int r = g * 64 + lane;
-                const uint64_t m = __ballot(r < K && (in[r] & 1));
-                if (lane == 0) ib[g] = m;
-            }
+            penc::pack_info(p.info_in + w * (uint64_t)K, K, ib, lane);
         }
         wave_sync();
         if (p.gen && p.info) {
             uint8_t *out = p.info + w * (uint64_t)K;
             for (int r = lane; r < K; r += 64) out[r] = (uint8_t)((ib[r >> 6] >> (r & 63)) & 1ull);
         }
-        // ---- u: information bits at the unfrozen symbols, zeros at the frozen ones
-        for (int g = 0; g < u64s; ++g) {
-            const int i = g * 64 + lane;
-            const int r = i < U ? (int)t.inforank[i] : -1;
-            const uint64_t m = __ballot(r >= 0 && ((ib[r >> 6] >> (r & 63)) & 1ull));
-            if (lane == 0) ua[g] = m;
-        }
-        wave_sync();
-        // ---- dynamic frozen symbols in symbol order: the XOR of the constraint's earlier terms
-        {
-            uint32_t *u32 = reinterpret_cast<uint32_t *>(ua);
-            for (int d = 0; d < t.ndyn; ++d) {
-                const uint32_t a = t.dynoff[d], e = t.dynoff[d + 1] - 1u;  // terms [a, e), the symbol at e
-                uint32_t v = 0;
-                for (uint32_t q = a + (uint32_t)lane; q < e; q += 64) v ^= ubit(u32, t.dynterm[q]);
-                const uint32_t par = (uint32_t)__popcll(__ballot(v != 0)) & 1u;
-                const int sym = t.dynterm[e];
-                if (par && lane == 0) u32[sym >> 5] |= 1u << (sym & 31);
-                wave_sync();
-            }
-        }
+        // ---- u: information bits at the unfrozen symbols, zeros at the static frozen ones, the
+        // dynamic frozen symbols in symbol order (polar_enc_device.h)
+        penc::build_u(t, ib, ua, lane);
         // ---- the transform, innermost layer first (MixedKernelEncoder.cpp:159-170): each block
         // of `next` symbols, viewed as l rows of `stride`, becomes (rows) x K
         uint64_t *src = ua, *dst = ub;

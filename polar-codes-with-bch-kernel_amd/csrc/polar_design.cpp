@@ -2,7 +2,9 @@
 // the bchk_kernel_bec_capacity / bchk_kernel_write_file / bchk_polar_design_bec block): the
 // capacity evaluation of a kernel's BEC polarisation table, the kernel-file writer that stores
 // that table where the reference reads it, and the layer-by-layer capacity recursion that
-// picks the frozen set of a code specification.
+// picks the frozen set of a code specification. Also the Monte-Carlo AWGN design
+// (bchk_polar_design_genie): the frozen set ranked by the genie-aided error statistics of
+// bchk_polar_genie_run (polar_host.cpp, polar_genie.hip).
 //
 // Reference: CBECCapacityEvaluator (out/external/CapacityEvaluator.cpp:100-140: the table's
 // file layout and GetSubchannelCapacity's Horner rule), CArikanKernel::GetSubchannelCapacity
@@ -241,6 +243,70 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
     *needed = text.size() + 1;
     if (!spec || spec_len < *needed) return dfail(BCHK_EINVAL, "specification needs %zu bytes, buffer has %zu", *needed, spec ? spec_len : (size_t)0);
     std::memcpy(spec, text.c_str(), *needed);
+    return BCHK_OK;
+}
+
+// Monte-Carlo AWGN design: the symbols ranked by their genie-aided error statistics
+// (bchk_polar_genie_run) over `words` words of the stream `seed` at snr_db, decoded as the code
+// with the lowest indices frozen (the rate K / U fixes the noise deviation; the statistics do
+// not depend on the frozen set, every earlier symbol being fed back true).
+int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words, uint64_t seed,
+                            int device, uint64_t *err, int64_t *soft, char *spec, size_t spec_len, size_t *needed) {
+    if (needed) *needed = 0;
+    if (!layers || !needed) return dfail(BCHK_EINVAL, "NULL argument");
+    if (words == 0 || words > (1ull << 31)) return dfail(BCHK_EINVAL, "words must be 1..2^31");
+    std::istringstream in(layers);
+    std::vector<std::string> names;
+    for (std::string s; in >> s;) names.push_back(s);
+    const int n = (int)names.size();
+    if (n < 1 || n > kMaxLayers) return dfail(BCHK_EINVAL, "%d layers unsupported", n);
+    long U = 1;
+    for (int j = 0; j < n; ++j) {
+        const std::string &name = names[j];
+        if (name == "A" || name == "a") {
+            U *= 2;
+        } else if (name[0] == '-' || name[0] == '<') {
+            std::vector<uint8_t> Km;
+            std::vector<double> tab;
+            bool has = false;
+            int l = 0;
+            if (int rc = read_kernel_file(name, kdir, &l, Km, tab, &has)) return rc;
+            if (!invertible(Km, l)) return dfail(BCHK_EINVAL, "Kernel is singular (%s)", name.c_str() + 1);
+            U *= l;
+        } else {
+            return dfail(BCHK_EINVAL, "Unknown kernel %s", name.c_str());
+        }
+        if (U > kMaxLength) return dfail(BCHK_EINVAL, "length %ld exceeds %ld", U, kMaxLength);
+    }
+    if (K <= 0 || K > U) return dfail(BCHK_EINVAL, "dimension %d outside 1..%ld", K, U);
+    std::string head = std::to_string(U) + " " + std::to_string(K) + " 0 " + std::to_string(n) + " 0 0\n";
+    for (int j = 0; j < n; ++j) head += names[j] + (j + 1 < n ? " " : "\n");
+    std::string base = head;
+    for (long f = 0; f < U - K; ++f) base += "1 " + std::to_string(f) + "\n";
+    bchk_polar *pc = nullptr;
+    if (int rc = bchk_polar_create_kdir(base.c_str(), kdir, 1, device, &pc)) return rc;
+    std::vector<uint64_t> e(U);
+    std::vector<int64_t> s(U);
+    const int rc = bchk_polar_genie_run(pc, snr_db, words, seed, 0, 0, e.data(), s.data(), nullptr);
+    bchk_polar_destroy(pc);
+    if (rc) return rc;
+    // i is better than j: fewer errors, then the larger soft sum, then the higher index
+    std::vector<int> order(U);
+    for (int i = 0; i < U; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](int a, int b) {
+        if (e[a] != e[b]) return e[a] < e[b];
+        if (s[a] != s[b]) return s[a] > s[b];
+        return a > b;
+    });
+    std::vector<int> frozen(order.begin() + K, order.end());
+    std::sort(frozen.begin(), frozen.end());
+    std::string text = head;
+    for (int f : frozen) text += "1 " + std::to_string(f) + "\n";
+    *needed = text.size() + 1;
+    if (!spec || spec_len < *needed) return dfail(BCHK_EINVAL, "specification needs %zu bytes, buffer has %zu", *needed, spec ? spec_len : (size_t)0);
+    std::memcpy(spec, text.c_str(), *needed);
+    if (err) std::copy(e.begin(), e.end(), err);
+    if (soft) std::copy(s.begin(), s.end(), soft);
     return BCHK_OK;
 }
 

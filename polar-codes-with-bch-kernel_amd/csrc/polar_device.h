@@ -194,6 +194,49 @@ constexpr uint32_t polar_gen_wave_bytes(int U, int K) {
     return 8u * (uint32_t)(2 * ((K + 127) / 128) + 2) + 16u * (uint32_t)((U + 63) / 64);
 }
 
+// ---- genie-aided SC (polar_genie.hip): one path per word in the mixed layout above (every
+// code, all-Arikan ones included), fed back with the sent u instead of its decisions. The
+// kernel writes per word the U decision LLRs and the U rebuilt encoder inputs as rows; a second
+// kernel sums the columns into the per-symbol error counts and soft sums (integers: the result
+// does not depend on grids, batch splits or the order of waves).
+struct PolarGenieParams {
+    PolarEncTables t;        // u is rebuilt as polar_gen_kernel does (polar_enc_device.h)
+    const uint8_t *info_tx;  // [B][K] sent information bits
+    const float *llr;        // [B][N] channel LLRs
+    float *dec_llr;          // [B][U] decision LLRs (rows)
+    uint8_t *u;              // [B][U] encoder inputs (rows)
+    const int16_t *symmap;   // [U] LoadLLRs
+    const uint32_t *tent, *tbase;  // trellis tables (PolarMixedParams)
+    const uint8_t *tlog;
+    int32_t tstates;
+    uint32_t B;
+    int32_t ssize, csize, osize;
+    int32_t outer[kPolarMaxLayers + 1];
+    int32_t soff[kPolarMaxLayers + 1], coff[kPolarMaxLayers + 1], ooff[kPolarMaxLayers];
+    uint8_t arikan[kPolarMaxLayers], trellis[kPolarMaxLayers];
+};
+// LDS of one wave: channel LLRs, S, C, offset states, kernel rows, the trellis metric buffers
+// (2 x tstates floats), the packed information bits and the packed u
+struct PolarGenieLayout {
+    int o_S, o_C, o_O, o_rows, o_tm, o_ib, o_u;
+    uint32_t bytes;
+};
+__host__ __device__ inline PolarGenieLayout polar_genie_layout(int U, int K, int ssize, int csize, int osize, int nl,
+                                                               int tstates) {
+    PolarGenieLayout o;
+    o.o_S = (4 * U + 15) & ~15;
+    o.o_C = o.o_S + 4 * ssize;
+    o.o_O = o.o_C + csize;
+    o.o_rows = (o.o_O + osize + 15) & ~15;
+    o.o_tm = o.o_rows + 8 * kPolarMaxKernel * nl;
+    o.o_ib = o.o_tm + 8 * tstates;
+    o.o_u = o.o_ib + 8 * (2 * ((K + 127) / 128) + 2);
+    o.bytes = (uint32_t)((o.o_u + 8 * ((U + 63) / 64) + 15) & ~15);
+    return o;
+}
+// words of one launch a workgroup of the column-sum kernel covers for its 64 symbols
+constexpr uint32_t kGenieSumRows = 32;
+
 // Packed partial sums of the all-Arikan kernel (polar_sclist.hip): per path C_0 (U bits,
 // the codeword) then C_λ (U >> (λ-1) bits, λ = 1..n), each starting on a 32-bit word; the
 // path stride is odd, so the same word of different paths falls in different banks. Writes

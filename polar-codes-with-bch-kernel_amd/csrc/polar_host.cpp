@@ -5,7 +5,8 @@
 // 27-39, out/external/MixedKernelListDecoder.cpp:9, :211-268) and CMixedKernelEncoder::Encode
 // (out/external/MixedKernelEncoder.cpp:142-177). All decoding runs on the GPU. Also the
 // simulation front-end (polar_channel.hip): encode, AWGN words, the simulator's counters and
-// the Eb/N0 sweep of CSimulator (out/external/Simulator.cpp:104-110, :139-335).
+// the Eb/N0 sweep of CSimulator (out/external/Simulator.cpp:104-110, :139-335), and the
+// genie-aided SC runs (polar_genie.hip) behind bchk_polar_genie_device / bchk_polar_genie_run.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,6 +33,10 @@ hipError_t launch_polar_mixed(const PolarMixedParams &p, int grid, size_t lds, h
 const void *polar_mixed_kernel_ptr();
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
 hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s);
+hipError_t launch_polar_genie(const PolarGenieParams &p, int grid, size_t lds, hipStream_t s);  // polar_genie.hip
+hipError_t launch_polar_genie_sum(const float *dec_llr, const uint8_t *u, uint32_t B, int U, uint64_t *err,
+                                  int64_t *soft, hipStream_t s);
+const void *polar_genie_kernel_ptr();
 void set_last_error(const char *msg);  // bchk_host.cpp: the message bchk_last_error returns
 }  // namespace bchk
 
@@ -111,6 +116,11 @@ struct bchk_polar {
     PBuf rstate, rsave, unfinished;
     uint64_t budget_ticks = 0;  // 100 MHz ticks per launch, 0 = one launch per call
     uint64_t launches_last = 0; // launches the last budgeted call took
+    // genie-aided SC (polar_genie.hip): the one-path layout, set up by the first genie call
+    PolarGenieParams gp{};
+    size_t genie_lds = 0;
+    int genie_grid = 0;
+    PBuf gdec, gu, gsum;  // decision-LLR and u rows when the caller passes none; bchk_polar_genie_run's counters
 };
 
 namespace {
@@ -377,6 +387,26 @@ int parse_spec(bchk_polar *c, const char *spec, const char *kdir) {
     return 0;
 }
 
+// the mixed layout of one path (oracle/polar_oracle.c plr_decode's offsets)
+void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
+    const int nl = c->n;
+    m.nl = nl;
+    m.outer[0] = c->U;
+    for (int j = 0; j < nl; ++j) {
+        m.ksize[j] = c->ksize[j];
+        m.arikan[j] = c->arikan[j];
+        m.outer[j + 1] = m.outer[j] / c->ksize[j];
+    }
+    int so = 0, co = 0, oo = 0;
+    for (int lam = 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
+    for (int lam = 0; lam <= nl; ++lam) { m.coff[lam] = co; co += lam ? m.outer[lam] * c->ksize[lam - 1] : m.outer[0]; }
+    for (int j = 0; j < nl; ++j) { m.ooff[j] = oo; if (!c->arikan[j]) oo += c->ksize[j] * m.outer[j + 1]; }
+    m.soff[0] = 0;
+    m.ssize = (so + 3) & ~3;
+    m.csize = (co + 15) & ~15;
+    m.osize = (oo + 15) & ~15;
+}
+
 }  // namespace
 
 extern "C" {
@@ -398,24 +428,10 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         delete c;
         return rc;
     }
-    if (c->mixed) {  // the mixed layout (oracle/polar_oracle.c plr_decode's offsets)
+    if (c->mixed) {
         PolarMixedParams &m = c->mp;
         const int nl = c->n;
-        m.nl = nl;
-        m.outer[0] = c->U;
-        for (int j = 0; j < nl; ++j) {
-            m.ksize[j] = c->ksize[j];
-            m.arikan[j] = c->arikan[j];
-            m.outer[j + 1] = m.outer[j] / c->ksize[j];
-        }
-        int so = 0, co = 0, oo = 0;
-        for (int lam = 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
-        for (int lam = 0; lam <= nl; ++lam) { m.coff[lam] = co; co += lam ? m.outer[lam] * c->ksize[lam - 1] : m.outer[0]; }
-        for (int j = 0; j < nl; ++j) { m.ooff[j] = oo; if (!c->arikan[j]) oo += c->ksize[j] * m.outer[j + 1]; }
-        m.soff[0] = 0;
-        m.ssize = (so + 3) & ~3;
-        m.csize = (co + 15) & ~15;
-        m.osize = (oo + 15) & ~15;
+        mixed_layout(c, m);
         // matrix layers from the trellis threshold up take their LLRs from the trellis; those
         // larger than the trellis limit (or from BCHK_POLAR_ML up) from the exact
         // ordered-statistics search
@@ -547,6 +563,9 @@ void bchk_polar_destroy(bchk_polar *c) {
     c->txcw.release();
     c->flags.release();
     c->cnt8.release();
+    c->gdec.release();
+    c->gu.release();
+    c->gsum.release();
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -896,6 +915,136 @@ int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int
     }
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (words_decoded) *words_decoded = decoded;
+    return 0;
+}
+
+// The genie kernel's layout, LDS size and persistent grid (once per context).
+static int genie_setup(bchk_polar *c) {
+    if (c->genie_grid) return 0;
+    PolarMixedParams m{};
+    if (c->mixed)
+        m = c->mp;
+    else
+        mixed_layout(c, m);  // an all-Arikan code in the mixed layout: the same f/g arithmetic
+    PolarGenieParams &g = c->gp;
+    g.ssize = m.ssize;
+    g.csize = m.csize;
+    g.osize = m.osize;
+    g.tstates = m.tstates;
+    for (int j = 0; j <= c->n; ++j) {
+        g.outer[j] = m.outer[j];
+        g.soff[j] = m.soff[j];
+        g.coff[j] = m.coff[j];
+    }
+    for (int j = 0; j < c->n; ++j) {
+        g.ooff[j] = m.ooff[j];
+        g.arikan[j] = m.arikan[j];
+        g.trellis[j] = m.trellis[j];
+    }
+    const size_t lds = polar_genie_layout(c->U, c->K, g.ssize, g.csize, g.osize, c->n, g.tstates).bytes;
+    if (lds > 160 * 1024)
+        return pfail(BCHK_EINVAL, "genie-aided SC of length %d needs %zu B of LDS (> 160 KiB)", c->U, lds);
+    const void *fn = polar_genie_kernel_ptr();
+    if (lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    int per_cu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, lds) != hipSuccess || per_cu <= 0) {
+        per_cu = 1;
+        (void)hipGetLastError();
+    }
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device) != hipSuccess || cus <= 0) {
+        cus = 1;
+        (void)hipGetLastError();
+    }
+    int grid = per_cu * cus;
+    if (const char *e = getenv("BCHK_POLAR_GRID")) grid = std::max(1, atoi(e));
+    if (getenv("BCHK_POLAR_DEBUG"))
+        fprintf(stderr, "bchk_polar genie: U=%d lds=%zu per_cu=%d CUs=%d grid=%d\n", c->U, lds, per_cu, cus, grid);
+    c->genie_lds = lds;
+    c->genie_grid = grid;
+    return 0;
+}
+
+// Genie-aided SC of one batch (polar_genie.hip): the decision LLR of every symbol with the
+// true earlier symbols fed back, and the per-symbol counters added into d_err / d_soft.
+int bchk_polar_genie_device(bchk_polar *c, const uint8_t *d_info_tx, const float *d_llr, size_t B, uint64_t *d_err,
+                            int64_t *d_soft, float *d_dec_llr, uint8_t *d_u, void *stream) {
+    if (!c || (B && ((c->K && !d_info_tx) || !d_llr || !d_err || !d_soft))) return pfail(BCHK_EINVAL, "NULL argument");
+    if (c->mixed && c->mp.any_ml)
+        return pfail(BCHK_EINVAL, "genie-aided SC does not take a code with a search layer (a matrix kernel above %d, "
+                                  "or BCHK_POLAR_ML)", kPolarMaxTrellisKernel);
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    if (B == 0) return 0;
+    int rc;
+    if ((rc = genie_setup(c))) return rc;
+    // rows the caller does not want go to scratch the context owns (grown on demand)
+    if (!d_dec_llr) {
+        if ((rc = c->gdec.ensure(B * (size_t)c->U * sizeof(float)))) return rc;
+        d_dec_llr = (float *)c->gdec.p;
+    }
+    if (!d_u) {
+        if ((rc = c->gu.ensure(B * (size_t)c->U))) return rc;
+        d_u = (uint8_t *)c->gu.p;
+    }
+    PolarGenieParams p = c->gp;
+    p.t = enc_tables(c);
+    p.info_tx = d_info_tx;
+    p.llr = d_llr;
+    p.dec_llr = d_dec_llr;
+    p.u = d_u;
+    p.symmap = reinterpret_cast<const int16_t *>(c->d_tab + c->off_symmap);
+    p.tent = reinterpret_cast<const uint32_t *>(c->d_tab + c->off_tent);
+    p.tbase = reinterpret_cast<const uint32_t *>(c->d_tab + c->off_tbase);
+    p.tlog = c->d_tab + c->off_tlog;
+    p.B = (uint32_t)B;
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    PHIP_TRY(launch_polar_genie(p, (int)std::min<size_t>((size_t)c->genie_grid, B), c->genie_lds, s));
+    PHIP_TRY(launch_polar_genie_sum(d_dec_llr, d_u, (uint32_t)B, c->U, d_err, d_soft, s));
+    return 0;
+}
+
+// Words [word0, word0 + words) of the stream `seed` at snr_db through the genie kernel, in
+// batches; the sums are integers, so the result does not depend on `batch`.
+int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t seed, uint64_t word0, size_t batch,
+                         uint64_t *err, int64_t *soft, double *seconds) {
+    if (!c || !err || !soft) return pfail(BCHK_EINVAL, "NULL argument");
+    if (words == 0 || words > (1ull << 31))
+        return pfail(BCHK_EINVAL, "words must be 1..2^31 (the soft sums stay inside 64 bits)");
+    if (c->mixed && c->mp.any_ml)
+        return pfail(BCHK_EINVAL, "genie-aided SC does not take a code with a search layer (a matrix kernel above %d, "
+                                  "or BCHK_POLAR_ML)", kPolarMaxTrellisKernel);
+    if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
+    int rc;
+    if ((rc = genie_setup(c))) return rc;
+    const size_t N = (size_t)c->N, K = (size_t)c->K, U = (size_t)c->U;
+    size_t Bm = batch;
+    if (!Bm) {  // a few rounds of the persistent grid, within 256 MiB of buffers
+        Bm = std::max<size_t>(4096, 16 * (size_t)c->genie_grid);
+        Bm = std::max<size_t>(1, std::min(Bm, (size_t(1) << 28) / (4 * N + K + 5 * U)));
+    }
+    Bm = (size_t)std::min<uint64_t>(Bm, words);
+    if ((rc = c->llr.ensure(Bm * N * sizeof(float))) || (rc = c->txinfo.ensure(Bm * K)) ||
+        (rc = c->gdec.ensure(Bm * U * sizeof(float))) || (rc = c->gu.ensure(Bm * U)) || (rc = c->gsum.ensure(16 * U)))
+        return rc;
+    const hipStream_t s = c->stream;
+    uint64_t *d_err = (uint64_t *)c->gsum.p;
+    int64_t *d_soft = (int64_t *)(d_err + U);
+    const auto t0 = std::chrono::steady_clock::now();
+    PHIP_TRY(hipMemsetAsync(c->gsum.p, 0, 16 * U, s));
+    for (uint64_t done = 0; done < words;) {
+        const size_t nb = (size_t)std::min<uint64_t>(Bm, words - done);
+        if ((rc = bchk_polar_generate_device(c, snr_db, nb, seed, word0 + done, (uint8_t *)c->txinfo.p, nullptr,
+                                             (float *)c->llr.p, s)) ||
+            (rc = bchk_polar_genie_device(c, (const uint8_t *)c->txinfo.p, (const float *)c->llr.p, nb, d_err, d_soft,
+                                          nullptr, nullptr, s)))
+            return rc;
+        done += nb;
+    }
+    std::vector<uint64_t> h(2 * U);
+    PHIP_TRY(hipMemcpyAsync(h.data(), c->gsum.p, 16 * U, hipMemcpyDeviceToHost, s));
+    PHIP_TRY(hipStreamSynchronize(s));
+    memcpy(err, h.data(), 8 * U);
+    memcpy(soft, h.data() + U, 8 * U);
+    if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
 }
 

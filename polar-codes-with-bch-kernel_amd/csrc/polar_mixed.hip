@@ -21,18 +21,16 @@
 #include <stdint.h>
 
 #include "polar_device.h"
+#include "polar_llr_device.h"
 
 namespace bchk {
 
 namespace {
 
+using pllr::wsync;
+
 constexpr uint32_t kUninitM = 0xFFFFFFFFu;
 
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ float rdlf_m(float v, int l) {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
 }
@@ -66,29 +64,6 @@ struct MStack {  // TVMemoryEngine's path-index stack with lazy initialisation (
         if (lane == top) slot = x;
     }
 };
-
-// min over the words of one half of the coset (CTrellisKernelProcessor::GetLLRs, :272-292):
-// words c = XOR of rows phase+1 .. l-1 selected by v, v = first, first + step, ...; metric of
-// c (b = 0) and c ^ row[phase] (b = 1) against the hard decision (l <= 32)
-__device__ __forceinline__ void coset_min(const uint64_t *rows, int l, int phase, const float *ay, uint64_t hd,
-                                          uint32_t first, uint32_t step, float &b0, float &b1) {
-    const int nfree = l - phase - 1;
-    const uint32_t nw = 1u << nfree;
-    for (uint32_t v = first; v < nw; v += step) {
-        uint64_t c = 0;
-        for (int r = 0; r < nfree; ++r)
-            if ((v >> r) & 1u) c ^= rows[phase + 1 + r];
-        const uint64_t d0 = c ^ hd, d1 = d0 ^ rows[phase];
-        float m0 = 0.0f, m1 = 0.0f;  // left to right (:279-282)
-        for (int j = 0; j < l; ++j) {
-            if ((d0 >> j) & 1ull) m0 += ay[j];
-            if ((d1 >> j) & 1ull) m1 += ay[j];
-        }
-        b0 = m0 < b0 ? m0 : b0;
-        b1 = m1 < b1 ? m1 : b1;
-    }
-}
-
 
 // ---- exact kernel LLRs by an ordered-statistics search (matrix kernels beyond the trellis
 // limit, e.g. the 64 x 64 extended-BCH kernel of root bchCoder.cpp:356-389 makeMatrix).
@@ -385,6 +360,8 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     auto Sof = [&](int q, int lam) -> float * { return lam == 0 ? chan : S + (size_t)q * p.ssize + p.soff[lam]; };
     auto Cof = [&](int q, int lam) -> uint8_t * { return C + (size_t)q * p.csize + p.coff[lam]; };
     auto Oof = [&](int q, int j) -> uint8_t * { return O + (size_t)q * p.osize + p.ooff[j]; };
+    auto pathof = [&](int k) -> int { return (int)act[k]; };  // the k-th active path
+    const pllr::Trellis tr{p.tent, p.tbase, p.tlog, tmet, p.tstates};
     auto list_act = [&](uint32_t active) {
         if (mine && ((active >> lane) & 1u)) act[__builtin_popcount(active & ((1u << lane) - 1u))] = (uint32_t)lane;
         wsync();
@@ -538,38 +515,13 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                 const int d = p.outer[j + 1], l = p.ksize[j];
                 const int tot = nact * d;
                 if (p.arikan[j]) {
-                    for (int it = lane; it < tot; it += 64) {
-                        const int q = (int)act[it / d], s = it % d;
-                        const float *src = Sof(q, j);
-                        float *dst = Sof(q, j + 1);
-                        const float a = src[s], b = src[d + s];
-                        float r;
-                        if (loc) {  // SoftCombine (:39-50)
-                            r = Cof(q, j + 1)[s] ? b - a : b + a;
-                        } else {    // SoftXOR (:54-80)
-                            const float fa = fabsf(a), fb = fabsf(b), mn = fa < fb ? fa : fb;
-                            r = __uint_as_float(__float_as_uint(mn) |
-                                                ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-                        }
-                        dst[s] = r;
-                    }
+                    pllr::arikan_llrs(j, loc, d, tot, lane, pathof, Sof, Cof);
                     wsync();
                     continue;
                 }
                 // matrix layer: offset state (:240-262), then the min-sum LLR per element
                 const uint64_t *kr = rows + kPolarMaxKernel * j;
-                for (int it = lane; it < tot && !resume_here; it += 64) {  // (applied before a suspension)
-                    const int q = (int)act[it / d], s = it % d;
-                    uint8_t *off = Oof(q, j);
-                    if (!loc) {
-                        for (int i = 0; i < l; ++i) off[i * d + s] = 0;
-                    } else {
-                        const uint8_t kn = Cof(q, j + 1)[(loc - 1) * d + s];
-                        if (kn)
-                            for (int i = 0; i < l; ++i)
-                                if ((kr[loc - 1] >> i) & 1ull) off[i * d + s] ^= 1u;
-                    }
-                }
+                if (!resume_here) pllr::matrix_offsets(kr, j, l, loc, d, tot, lane, pathof, Cof, Oof);  // (applied before a suspension)
                 wsync();
                 if (p.ml[j]) {
                     // exact ordered-statistics search (kernels larger than the trellis limit):
@@ -599,95 +551,10 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                     continue;
                 }
                 if (p.trellis[j]) {
-                    // CTrellisKernelProcessor::GetLLRs (:260-292) as a pull-form Viterbi: a state
-                    // of depth dd + 1 takes the smaller of its (at most two) predecessors' metrics,
-                    // each plus |Y| when its edge label differs from the hard decision (min
-                    // commutes with the monotone float add, so the values are the reference's).
-                    // G lanes per item (G = states of the phase's widest depth, at most 64).
-                    const int tp = j * kPolarMaxKernel + loc;
-                    const uint8_t *lgp = p.tlog + (size_t)tp * (kPolarMaxKernel + 1);
-                    const uint32_t *ent0 = p.tent + p.tbase[tp];
-                    int ab = 0;
-                    for (int dd = 1; dd <= l; ++dd) ab = lgp[dd] > ab ? lgp[dd] : ab;
-                    const int stride = 1 << ab, G = stride < 64 ? stride : 64, ipr = 64 / G;
-                    const int slot = lane / G, sub = lane % G;
-                    for (int base = 0; base < tot; base += ipr) {
-                        const int it = base + slot;
-                        const bool have = slot < ipr && it < tot;
-                        int q = 0, s = 0;
-                        if (have) {
-                            q = (int)act[it / d];
-                            s = it % d;
-                        }
-                        const float *src = Sof(q, j);
-                        const uint8_t *off = Oof(q, j);
-                        float *m0 = tmet + slot * stride, *m1 = tmet + p.tstates + slot * stride;
-                        if (have && sub == 0) m0[0] = 0.0f;
-                        wsync();
-                        const uint32_t *e = ent0;
-                        for (int dd = 0; dd < l; ++dd) {
-                            const int n1 = 1 << lgp[dd + 1];
-                            if (have) {
-                                const float v = src[dd * d + s];
-                                const float yv = off[dd * d + s] ? -v : v;
-                                const bool hd = yv < 0.0f;  // HD = Y < 0 (:270)
-                                const float ay = fabsf(yv);
-                                for (int S1 = sub; S1 < n1; S1 += G) {
-                                    const uint32_t w = e[S1], a = w & 0xFFFFu, b = w >> 16;
-                                    float x = m0[a & kTrellisState];
-                                    if (((a & kTrellisZ) != 0u) != hd) x = x + ay;
-                                    if (b & kTrellisValid) {
-                                        float xb = m0[b & kTrellisState];
-                                        if (((b & kTrellisZ) != 0u) != hd) xb = xb + ay;
-                                        x = xb < x ? xb : x;
-                                    }
-                                    m1[S1] = x;
-                                }
-                            }
-                            wsync();
-                            float *tt = m0;
-                            m0 = m1;
-                            m1 = tt;
-                            e += n1;
-                        }
-                        if (have && sub == 0) Sof(q, j + 1)[s] = m0[1] - m0[0];  // (:292)
-                        wsync();
-                    }
+                    pllr::trellis_llrs(tr, j, l, loc, d, tot, lane, pathof, Sof, Oof);
                     continue;
                 }
-                // lanes per item: the coset split when items are fewer than lanes
-                int lpi = 1;
-                const int nfree = l - loc - 1;
-                while (lpi * 2 * tot <= 64 && (lpi * 2) <= (1 << (nfree < 6 ? nfree : 6))) lpi *= 2;
-                const int span = 64 / lpi * lpi;  // lanes used per round
-                for (int base = 0; base < tot * lpi; base += span) {
-                    const int g = base + lane;
-                    const bool have = lane < span && g < tot * lpi;
-                    const int it = g / lpi, sub = g % lpi;
-                    float b0 = __int_as_float(0x7F800000), b1 = __int_as_float(0x7F800000);
-                    int q = 0, s = 0;
-                    if (have) {
-                        q = (int)act[it / d];
-                        s = it % d;
-                        const float *src = Sof(q, j);
-                        const uint8_t *off = Oof(q, j);
-                        float ay[kPolarMaxTrellisKernel];  // enumerated layers: l <= 32
-                        uint64_t hd = 0;
-                        for (int jj = 0; jj < l; ++jj) {
-                            const float v = src[jj * d + s];
-                            const float yv = off[jj * d + s] ? -v : v;
-                            if (yv < 0.0f) hd |= 1ull << jj;  // HD = Y < 0 (:276)
-                            ay[jj] = fabsf(yv);
-                        }
-                        coset_min(kr, l, loc, ay, hd, (uint32_t)sub, (uint32_t)lpi, b0, b1);
-                    }
-                    for (int o = 1; o < lpi; o <<= 1) {  // min over the item's lanes (exact)
-                        const float x0 = __shfl_xor(b0, o, 64), x1 = __shfl_xor(b1, o, 64);
-                        b0 = x0 < b0 ? x0 : b0;
-                        b1 = x1 < b1 ? x1 : b1;
-                    }
-                    if (have && sub == 0) Sof(q, j + 1)[s] = b1 - b0;  // (:292)
-                }
+                pllr::enum_llrs(kr, j, l, loc, d, tot, lane, pathof, Sof, Oof);
                 wsync();
             }
             if (yielded) break;
@@ -762,32 +629,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             }
             // ---- IterativelyUpdateC (KernelListEngine.cpp:266-315): finished blocks are
             // multiplied by their kernel into the parent layer's inputs
-            {
-                int lam = nl, stride = 1;
-                uint32_t ph2 = (uint32_t)phi;
-                while (lam > 0 && (ph2 + 1) % (uint32_t)p.ksize[lam - 1] == 0) {
-                    const int l = p.ksize[lam - 1];
-                    const uint32_t psi = ph2 / (uint32_t)l;
-                    const int next = stride * l;
-                    const int phi0 = lam > 1 ? (int)(psi % (uint32_t)p.ksize[lam - 2]) * next : 0;
-                    const uint64_t *kr = rows + kPolarMaxKernel * (lam - 1);
-                    const int tot = nact * stride;
-                    for (int it = lane; it < tot; it += 64) {
-                        const int q = (int)act[it / stride], s = it % stride;
-                        const uint8_t *x = Cof(q, lam);
-                        uint8_t *yo = Cof(q, lam - 1) + phi0;
-                        // (y_i) = (x_j) K: y_i = XOR over rows j with K[j][i] (LinAlg.cpp:685-709)
-                        uint64_t yv = 0;
-                        for (int jj = 0; jj < l; ++jj)
-                            if (x[jj * stride + s] & 1u) yv ^= kr[jj];
-                        for (int i = 0; i < l; ++i) yo[i * stride + s] = (uint8_t)((yv >> i) & 1ull);
-                    }
-                    wsync();
-                    stride = next;
-                    ph2 = psi;
-                    --lam;
-                }
-            }
+            pllr::update_c(rows, p.ksize, nl, phi, nact, lane, pathof, Cof);
         }
         if (yielded) {  // suspended: outputs when it finishes in a later launch
             wsync();
