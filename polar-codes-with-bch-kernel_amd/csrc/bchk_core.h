@@ -151,13 +151,8 @@ __device__ __forceinline__ uint32_t gf_exp2(const uint8_t *ex, int la, int lb) {
 //     into the packed table (the cooperative kernel's LDS array was 88 % busy, half of it
 //     in bank conflicts, r05 PMC). handle = 64 log + 4 r, so a product is one
 //     v_add3 (a + b - 4 r) and one ds_read_b32, as before one add and one ds_read_u8.
-//   GfMul (m >= 7, the cooperative kernel's decoders, round 6): the whole product table
-//     [2^m][2^m] (64 KiB at m = 8) and the inverses in LDS; handle = the element itself, so
-//     lg() is free and a product is one lookup. The decoders' log lookups go away: Berlekamp-
-//     Massey re-logs C at every step (169 of its ~520 lookups at t = 15), the split test
-//     logs every coefficient it squares or reduces by (~120 of ~1 050).
 // Besides the products: val(h) = the element of handle h; pdiv(b) / div_by(a, pdiv(b)) =
-// a / b with the divisor's part computed once (a log for the log views, its inverse for GfMul).
+// a / b with the divisor's part computed once (a log).
 template <int M>
 struct GfPlain {
     static constexpr int N = Geo<M>::N, ZL = Geo<M>::ZL;
@@ -209,24 +204,6 @@ struct GfRep {
     }
     // any lane's handle (64 log + 4 r, 4 r < 64): the log alone
     __device__ __forceinline__ int plain(int h) const { return h / S; }
-};
-template <int M>
-constexpr int gf_mul_bytes() { return (1 << (2 * M)) + (1 << M); }  // products, then inverses
-template <int M>
-struct GfMul {
-    const uint8_t *mt;    // LDS: mt[a 2^m + b] = a b, then iv[a] = 1 / a (iv[0] = 0)
-    const uint16_t *lg_;  // the packed log table (plain logs for the Chien scan)
-    __device__ __forceinline__ int lg(uint32_t g) const { return (int)g; }
-    __device__ __forceinline__ uint32_t mul(int a, int b) const { return mt[(a << M) | b]; }
-    __device__ __forceinline__ uint32_t val(int h) const { return (uint32_t)h; }
-    __device__ __forceinline__ int zl() const { return 0; }
-    __device__ __forceinline__ int one() const { return 1; }
-    __device__ __forceinline__ bool is_zl(int h) const { return h == 0; }
-    __device__ __forceinline__ int pdiv(int b) const { return mt[(1 << (2 * M)) + b]; }
-    __device__ __forceinline__ int div_by(int a, int pb) const { return mt[(a << M) | pb]; }
-    __device__ __forceinline__ int div(int a, int b) const { return div_by(a, pdiv(b)); }
-    __device__ __forceinline__ int dbl(int h) const { return mt[(h << M) | h]; }  // h^2
-    __device__ __forceinline__ int plain(int h) const { return lg_[h]; }
 };
 // fills the replicated tables from the packed ones (a whole workgroup, before a barrier)
 template <int M>
@@ -653,11 +630,7 @@ __device__ __forceinline__ bool alg_decode_lanes_g(const GF &gf, const uint8_t *
 #pragma unroll
     for (int i = 0; i <= TMAX; ++i) lc[i] = gf.lg(C[i]);
     bool ok = act && (L <= t) && (deg >= 1);
-#if defined(BCHK_SPLIT_CUT)  // experiment builds only (wrong results): Berlekamp-Massey alone
-    ok = ok && lc[0] == 12345;
-#else
     if (ballot(ok)) ok = split_test<M, TMAX>(gf, lc, deg, ok) && ok;
-#endif
 #pragma unroll
     for (int s = 0; s < NW; ++s) E.w[s] = 0;
     for (uint64_t sm = ballot(ok); sm; sm &= sm - 1) {
@@ -675,8 +648,7 @@ __device__ __forceinline__ bool alg_decode_lanes_g(const GF &gf, const uint8_t *
 #pragma unroll
         for (int i = 0; i <= TMAX; ++i) {
             if (i <= dg) {
-                // the scan reads the packed exp table: plain logs (a lookup for GfMul, only
-                // for the rare successful lanes)
+                // the scan reads the packed exp table: plain logs
                 const int lti = gf.plain(__builtin_amdgcn_readlane(lc[i], src));
 #pragma unroll
                 for (int s = 0; s < NW; ++s) {
@@ -705,18 +677,13 @@ __device__ __forceinline__ bool alg_decode_lanes(const uint8_t *__restrict__ ex,
     return alg_decode_lanes_g<M, TMAX>(GfPlain<M>{ex, lg}, ex, Sw, t, E, act);
 }
 
-// The decoder a kernel uses: VALU BM for m <= 6 unless BCHK_GF_LDS is defined; m >= 7 the
-// split test (wave-collective).
+// The decoder a kernel uses: VALU BM for m <= 6; m >= 7 the split test (wave-collective).
 template <int M, int TMAX>
 __device__ __forceinline__ bool alg_decode_word(const uint8_t *ex, const uint16_t *lg,
                                                 const uint64_t *chien, const uint32_t *Sw, int t,
                                                 Mask<Geo<M>::NW> &E, bool act = true) {
-#ifndef BCHK_GF_LDS
     if constexpr (M <= 6) return alg_core_valu<M, TMAX>(chien, Sw, t, E);
-    else
-#endif
-    if constexpr (M >= 7) return alg_decode_lanes<M, TMAX>(ex, lg, Sw, t, E, act);
-    else return alg_core<M, TMAX>(ex, lg, chien, Sw, t, E);
+    else return alg_decode_lanes<M, TMAX>(ex, lg, Sw, t, E, act);
 }
 
 // Decoder::decode of ONE test word by a whole wave (its syndromes Sw wave-uniform): the

@@ -22,6 +22,7 @@
 #include <cstdlib>
 
 #include "bchk_core.h"
+#include "bchk_env.h"
 #include "bchk_launch.h"
 
 namespace bchk {
@@ -54,10 +55,6 @@ __device__ constexpr uint8_t kGreen16[60][2] = {
     {3, 5},  {6, 8},  {7, 9},  {10, 12},
     {3, 4},  {5, 6},  {7, 8},  {9, 10}, {11, 12},
     {6, 7},  {8, 9}};
-// accept: leave the flipped-position loops once no lane of the wave has another position
-#ifndef BCHK_ACC_BREAK
-#define BCHK_ACC_BREAK 1
-#endif
 
 template <int O>
 __device__ __forceinline__ void sort16(uint32_t *key) {
@@ -286,9 +283,7 @@ __device__ __forceinline__ FastRes fast_decide(const uint8_t *ex, const uint16_t
 #pragma unroll
         for (int j = 0; j < LMAX; ++j) {  // independent loads, issued together; only the
                                            // flipped positions' (no line fetched for others)
-#if BCHK_ACC_BREAK
             if (!ballot(v != 0ull)) break;  // no lane has a j-th flipped position
-#endif
             const int pj = (int)__builtin_ctzll(v);
             bool found = false;
             if (have_lo) {
@@ -311,9 +306,7 @@ __device__ __forceinline__ FastRes fast_decide(const uint8_t *ex, const uint16_t
         v = diff;
 #pragma unroll
         for (int j = 0; j < LMAX; ++j) {
-#if BCHK_ACC_BREAK
             if (!ballot(v != 0ull)) break;
-#endif
             if (v) l += fabs((2.0 * g[j]) / s2);
             v &= v - 1;
         }
@@ -400,11 +393,7 @@ __device__ __forceinline__ FastRes fast_decide(const uint8_t *ex, const uint16_t
     }
     between();
     const bool need1 = live && !bad && !ok0 && !zero0;
-#ifdef BCHK_FAST_NO_I1  // experiment builds: the i = 1 decode left to the exact kernels
-    if (false) {
-#else
     if (ballot(need1)) {
-#endif
         uint32_t S1[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) S1[w] = S0[w] ^ col[o0 * W + w];
@@ -978,14 +967,15 @@ static hipError_t launch_fast_ring(const SearchParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-// BCHK_FAST_RING=0 in the environment selects the staged kernel (measurements)
+// BCHK_FAST_RING=0 in the environment selects the staged kernel, BCHK_FAST_FULLSORT the full
+// sort without a stats record too (measurements); both read once, at the first launch
 static bool use_ring() {
-    static int r = -1;
-    if (r < 0) {
-        const char *e = getenv("BCHK_FAST_RING");
-        r = (e && atoi(e) == 0) ? 0 : 1;
-    }
-    return r != 0;
+    static const bool on = [] { bool r = true; env_bool("BCHK_FAST_RING", &r); return r; }();
+    return on;
+}
+static bool fast_fullsort() {
+    static const bool on = env_flag("BCHK_FAST_FULLSORT");
+    return on;
 }
 
 template <int M, int TMAX>
@@ -994,7 +984,7 @@ static hipError_t launch_fast_impl(const SearchParams &p, size_t lds, hipStream_
     constexpr int KMAX = (2 * TMAX < N - 1) ? 2 * TMAX : N - 1;
     if constexpr (KMAX + 2 <= 16) {
         // no stats record: the flags are not observable, selection suffices
-        if (!p.st && !getenv("BCHK_FAST_FULLSORT")) {
+        if (!p.st && !fast_fullsort()) {
             const bool ring = use_ring() && kRingPerCU * ring_lds_bytes<M>(p.td.bytes) <= 160 * 1024;
             return ring ? launch_fast_ring<M, TMAX>(p, s) : launch_fast_sel<M, TMAX, true>(p, lds, s);
         }
@@ -1258,9 +1248,7 @@ __device__ __forceinline__ LaneRes<Geo<M>::NW> lane_decide(const uint8_t *ex, co
         Mask<NW> v = diff;
 #pragma unroll
         for (int j = 0; j < LMAX; ++j) {  // the j-th flipped position, ascending
-#if BCHK_ACC_BREAK
             if (!ballot(j < m)) break;  // no lane has a j-th flipped position
-#endif
             int pj = -1;
 #pragma unroll
             for (int s = NW - 1; s >= 0; --s)
@@ -1273,9 +1261,7 @@ __device__ __forceinline__ LaneRes<Geo<M>::NW> lane_decide(const uint8_t *ex, co
         l = 0.0;
 #pragma unroll
         for (int j = 0; j < LMAX; ++j) {
-#if BCHK_ACC_BREAK
             if (!ballot(j < m)) break;
-#endif
             if (j < m) l += fabs((2.0 * g[j]) / s2);
         }
         double rs_lo = 0.0;

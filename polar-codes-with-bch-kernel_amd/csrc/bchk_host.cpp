@@ -10,6 +10,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstdarg>
 #include <cstdlib>
@@ -25,6 +26,7 @@
 
 #include "bchk.h"
 #include "bchk_device.h"
+#include "bchk_env.h"
 #include "bchk_launch.h"
 #include "bchk_stream.h"
 
@@ -274,7 +276,7 @@ int build_table(const Field &f, int t, HostTable &h) {
     }
     est = est / ((double)n * m) * 1.05 + 64;
     double maxload = 0.5;
-    if (const char *ml = getenv("BCHK_TAB_MAXLOAD")) maxload = std::min(0.95, std::max(0.05, atof(ml)));
+    env_double("BCHK_TAB_MAXLOAD", &maxload, 0.05, 0.95);
     h.bbits = 1;
     while ((double)(kTabSlots << h.bbits) * maxload < est) ++h.bbits;
     h.kbits = (uint32_t)tab_kbits(m, t);
@@ -447,7 +449,6 @@ struct bchk_ctx {
     uint32_t long_help_max = 0, long_share_min = 0;
     uint32_t long_epoch = 0;  // cooperative launches with jobs (tag generations)  // BCHK_LONG_HELP_MAX / BCHK_LONG_SHARE_MIN (0: defaults)
     DevBuf syn8;  // its hard-decision syndrome table (SearchParams::syn8)
-    DevBuf gfmul; // m >= 7: GF(2^m) products and inverses (SearchParams::gfmul)
     int tail_conc_blocks = 64;     // blocks of the concurrent tail kernel (BCHK_TAIL_BLOCKS)
     bool heavy_first = true;       // fast path queues likely heavy codewords first (BCHK_HEAVY_FIRST)
     // hybrid tail: a first-pass hand-off whose loop bound is below this goes to a cooperative
@@ -461,6 +462,9 @@ struct bchk_ctx {
     // syndrome decoding table (bchk_syndtab.h): built on first use, shared across contexts
     bool use_table = true;
     SyndTable tab{};
+    int coop_per_cu = 1;   // BCHK_COOP_PER_CU: cooperative workgroups per CU the LDS is sized for
+    int first_per_cu = 0;  // BCHK_FIRST_PER_CU (experiments; 0: by occupancy)
+    bool verbose = false;  // BCHK_VERBOSE: bchk_create prints its grids
     struct Ev {  // [fast, exact, coop, tail] x [start, end] of one pipeline of one call
         hipEvent_t e[8];
         bool first;  // the call's first pipeline
@@ -601,7 +605,6 @@ int launch_pipe(bchk_ctx *c, bchk_ctx::Pipe &P, bool first, int variant, const d
     p.J = c->J;
     p.variant = variant;
     p.fault = (uint32_t *)c->fault.p;
-    p.gfmul = (const uint8_t *)c->gfmul.p;  // null for m <= 6
     if (d_tx) {  // fused counters (zeroed by launch_search at allocation, then by every reduction)
         p.tx = d_tx;
         p.cnt = (unsigned long long *)c->cnt.p;
@@ -875,6 +878,48 @@ extern "C" {
 const char *bchk_last_error(void) { return g_err.c_str(); }
 const char *bchk_version(void) { return "bchk 0.1 (gfx950)"; }
 
+// The environment knobs of a context (DESIGN.md "Environment knobs"), read once here: a
+// variable set after bchk_create does not reach a live context.
+static void read_knobs(bchk_ctx *c) {
+    const int kMin = INT_MIN, kMax = INT_MAX;
+    int v;
+    env_bool("BCHK_LANE_PRE", &c->lane_pre);
+    env_bool("BCHK_LONG_HELP", &c->long_help);
+    if (env_int("BCHK_LONG_HELP_MAX", &v, 1, kMax)) c->long_help_max = (uint32_t)v;
+    if (env_int("BCHK_LONG_SHARE_MIN", &v, 8, kMax)) c->long_share_min = (uint32_t)v;
+    if (env_flag("BCHK_NO_FAST")) c->use_fast = false;
+    if (env_flag("BCHK_NO_TABLE")) c->use_table = false;
+    if (env_int("BCHK_CHUNK_LIMIT", &v, kMin, kMax)) c->chunk_limit = (uint32_t)v;
+    env_int("BCHK_LONG_REC", &c->long_rec, 0, 2);
+    env_bool("BCHK_COOP_CONCURRENT", &c->coop_concurrent);
+    if (env_flag("BCHK_NO_ANALYTIC")) c->analytic = false;
+    if (env_flag("BCHK_TAIL_DIAG")) c->tail_diag_on = true;
+    env_bool("BCHK_TAIL_CONCURRENT", &c->tail_concurrent);
+    env_bool("BCHK_TAIL_INLINE", &c->tail_inline);
+    env_bool("BCHK_AN_HELP", &c->an_help);
+    if (env_int("BCHK_FAST_RING_WAVES", &v, 2, 16)) c->fast_waves = (uint32_t)v;
+    if (env_int("BCHK_HEAVY_T", &v, 0, kMax)) c->heavy_t = (uint32_t)v;
+    if (env_int("BCHK_HEAVY_TMAX", &v, 0, kMax)) c->heavy_tmax = (uint32_t)v;
+    if (env_int("BCHK_FAST_MODE", &v, 0, kMax)) {
+        c->fast_mode = (uint32_t)v;
+#ifndef BCHK_EXPERIMENT_MODES
+        // modes 1 and 2 time parts of the ring kernel and give wrong results: experiment
+        // builds only, never the product library (a leftover variable must not yield a
+        // plausible-looking record)
+        if (c->fast_mode == 1u || c->fast_mode == 2u) c->fast_mode = 0;
+#endif
+    }
+    env_int("BCHK_TAIL_BLOCKS", &c->tail_conc_blocks, 1, kMax);
+    env_u64("BCHK_TAIL_MIN_BOUND", &c->tail_min_bound);
+    env_bool("BCHK_HEAVY_FIRST", &c->heavy_first);
+    env_int("BCHK_PIPES", &c->npipes, 1, 8);
+    uint64_t pm;
+    if (env_u64("BCHK_PIPE_MIN", &pm)) c->pipe_min = std::max<size_t>(64, pm);
+    env_int("BCHK_COOP_PER_CU", &c->coop_per_cu, 1, kMax);
+    env_int("BCHK_FIRST_PER_CU", &c->first_per_cu, 1, kMax);
+    c->verbose = env_flag("BCHK_VERBOSE");
+}
+
 int bchk_create(int m, int t, int J, double decoder_snr_db, int device, bchk_ctx **out) {
     if (!out) return fail(BCHK_EINVAL, "out is NULL");
     *out = nullptr;
@@ -943,59 +988,13 @@ int bchk_create(int m, int t, int J, double decoder_snr_db, int device, bchk_ctx
             return fail(BCHK_EHIP, "device setup failed: %s", hipGetErrorString(hipGetLastError()));
         }
     }
-    if (c->ks.gfmul) {
-        // the cooperative decoders' product table: [a][b] = a b, then [a] = 1 / a (0 for 0)
-        const int q = 1 << m, n = c->field.n;
-        std::vector<uint8_t> mt((size_t)q * q + q, 0);
-        for (int a = 1; a < q; ++a)
-            for (int b = 1; b < q; ++b)
-                mt[(size_t)a * q + b] = (uint8_t)c->field.alog[(c->field.log[a] + c->field.log[b]) % n];
-        for (int a = 1; a < q; ++a) mt[(size_t)q * q + a] = (uint8_t)c->field.alog[(n - c->field.log[a]) % n];
-        if (c->gfmul.ensure(mt.size()) != 0 ||
-            hipMemcpy(c->gfmul.p, mt.data(), mt.size(), hipMemcpyHostToDevice) != hipSuccess) {
-            bchk_destroy(c);
-            return fail(BCHK_EHIP, "device setup failed: %s", hipGetErrorString(hipGetLastError()));
-        }
-    }
-    if (const char *lp = getenv("BCHK_LANE_PRE")) c->lane_pre = atoi(lp) != 0;
-    if (const char *lh = getenv("BCHK_LONG_HELP")) c->long_help = atoi(lh) != 0;
-    if (const char *hm = getenv("BCHK_LONG_HELP_MAX")) c->long_help_max = (uint32_t)std::max(1, atoi(hm));
-    if (const char *sm = getenv("BCHK_LONG_SHARE_MIN")) c->long_share_min = (uint32_t)std::max(8, atoi(sm));
-    if (getenv("BCHK_NO_FAST")) c->use_fast = false;
-    if (getenv("BCHK_NO_TABLE")) c->use_table = false;
-    if (const char *cl = getenv("BCHK_CHUNK_LIMIT")) c->chunk_limit = (uint32_t)atoi(cl);
-    if (const char *lr = getenv("BCHK_LONG_REC")) c->long_rec = std::max(0, std::min(2, atoi(lr)));
-    if (const char *cc = getenv("BCHK_COOP_CONCURRENT")) c->coop_concurrent = atoi(cc) != 0;
-    if (getenv("BCHK_NO_ANALYTIC")) c->analytic = false;
-    if (getenv("BCHK_TAIL_DIAG")) c->tail_diag_on = true;
-    if (const char *tc = getenv("BCHK_TAIL_CONCURRENT")) c->tail_concurrent = atoi(tc) != 0;
-    if (const char *ti = getenv("BCHK_TAIL_INLINE")) c->tail_inline = atoi(ti) != 0;
-    if (const char *ah = getenv("BCHK_AN_HELP")) c->an_help = atoi(ah) != 0;
-    if (const char *fw = getenv("BCHK_FAST_RING_WAVES")) c->fast_waves = (uint32_t)std::max(2, std::min(16, atoi(fw)));
-    if (const char *ht = getenv("BCHK_HEAVY_T")) c->heavy_t = (uint32_t)std::max(0, atoi(ht));
-    if (const char *hx = getenv("BCHK_HEAVY_TMAX")) c->heavy_tmax = (uint32_t)std::max(0, atoi(hx));
-    if (const char *fm = getenv("BCHK_FAST_MODE")) {
-        c->fast_mode = (uint32_t)std::max(0, atoi(fm));
-#ifndef BCHK_EXPERIMENT_MODES
-        // modes 1 and 2 time parts of the ring kernel and give wrong results: experiment
-        // builds only, never the product library (a leftover variable must not yield a
-        // plausible-looking record)
-        if (c->fast_mode == 1u || c->fast_mode == 2u) c->fast_mode = 0;
-#endif
-    }
-    if (const char *tb = getenv("BCHK_TAIL_BLOCKS")) c->tail_conc_blocks = std::max(1, atoi(tb));
-    if (const char *tm = getenv("BCHK_TAIL_MIN_BOUND")) c->tail_min_bound = strtoull(tm, nullptr, 10);
-    if (const char *hf = getenv("BCHK_HEAVY_FIRST")) c->heavy_first = atoi(hf) != 0;
-    if (const char *np = getenv("BCHK_PIPES")) c->npipes = std::max(1, std::min(8, atoi(np)));
-    if (const char *pm = getenv("BCHK_PIPE_MIN")) c->pipe_min = std::max<size_t>(64, strtoull(pm, nullptr, 10));
+    read_knobs(c);
     c->lds_coop = tb + c->ks.coop_bytes;
     // one cooperative workgroup per CU by default (LDS sized past half the CU's 160 KB):
     // a heavy codeword's 16 waves then own the CU's four SIMDs, which shortens the longest
     // searches -- the critical path of a decode call -- and leaves the remaining wave slots
     // to the concurrent exact kernel
-    int coop_target = 1;
-    if (const char *cp = getenv("BCHK_COOP_PER_CU")) coop_target = std::max(1, atoi(cp));
-    if (coop_target == 1) c->lds_coop = std::max<size_t>(c->lds_coop, 82 * 1024);
+    if (c->coop_per_cu == 1) c->lds_coop = std::max<size_t>(c->lds_coop, 82 * 1024);
     // resident workgroups per CU of a kernel (its own registers; LDS as given)
     auto grid_of = [&](const void *fn, int threads, size_t lds) {
         if (lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1014,12 +1013,11 @@ int bchk_create(int m, int t, int J, double decoder_snr_db, int device, bchk_ctx
     }
     if (c->ks.tail) c->grid_tail = grid_of(c->ks.tail_ptr(), kWaveSize * kWavesPerBlock, c->lds_tail);
     if (c->ks.tail_tab) c->grid_tail_tab = grid_of(c->ks.tail_tab_ptr(), kWaveSize * kWavesPerBlock, c->lds_tail);
-    if (const char *fp = getenv("BCHK_FIRST_PER_CU")) {  // experiment: the first pass's workgroups per CU
-        const int per = std::max(1, atoi(fp));
-        c->grid = per * prop.multiProcessorCount;
-        if (c->ks.search_tab) c->grid_tab = per * prop.multiProcessorCount;
+    if (c->first_per_cu) {  // experiment: the first pass's workgroups per CU
+        c->grid = c->first_per_cu * prop.multiProcessorCount;
+        if (c->ks.search_tab) c->grid_tab = c->first_per_cu * prop.multiProcessorCount;
     }
-    if (getenv("BCHK_VERBOSE"))  // persistent grids (workgroups) and their LDS bytes
+    if (c->verbose)  // persistent grids (workgroups) and their LDS bytes
         fprintf(stderr, "bchk m=%d t=%d cus=%d grid %d (lds %zu) tab %d (lds %zu) tail %d tail_tab %d (lds %zu) coop %d coop_tab %d (lds %zu)\n",
                 m, t, prop.multiProcessorCount, c->grid, c->lds, c->grid_tab, c->lds_tab, c->grid_tail,
                 c->grid_tail_tab, c->lds_tail, c->grid_coop, c->grid_coop_tab, c->lds_coop);
@@ -1046,7 +1044,6 @@ void bchk_destroy(bchk_ctx *c) {
     c->synd.release();
     c->ok.release();
     c->syn8.release();
-    c->gfmul.release();
     if (c->d_tables) (void)hipFree(c->d_tables);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -1202,7 +1199,7 @@ static void gen_word(Eng &eng, const bchk_ctx *c, double sd, uint8_t *tx, double
 static int gen_threads() {
     int t = (int)std::thread::hardware_concurrency();
     if (const char *e = getenv("OMP_NUM_THREADS")) t = std::min(t > 0 ? t : 1, std::max(1, atoi(e)));
-    if (const char *e = getenv("BCHK_GEN_THREADS")) t = std::max(1, atoi(e));
+    env_int("BCHK_GEN_THREADS", &t, 1, INT_MAX);
     return std::max(1, std::min(t, 16));
 }
 

@@ -21,10 +21,12 @@
 #include <hip/hip_runtime.h>
 
 #include <float.h>
+#include <limits.h>
 #include <stdlib.h>
 #include <stdint.h>
 
 #include "bchk_core.h"
+#include "bchk_env.h"
 #include "bchk_launch.h"
 #include "bchk_search.h"
 
@@ -32,15 +34,11 @@ namespace bchk {
 
 // Waves per SIMD the registers must allow: 5 for the first pass with the syndrome table
 // (its LDS allows 5 workgroups per CU; left alone it takes 98 VGPRs, 4 waves), the compiler's
-// choice otherwise (the tail instance needs ~220). BCHK_SEARCH_WPE: experiment builds.
-#ifdef BCHK_SEARCH_WPE
-#define BCHK_SEARCH_ATTR __attribute__((amdgpu_waves_per_eu(BCHK_SEARCH_WPE)))
-#else
+// choice otherwise (the tail instance needs ~220).
 #ifndef BCHK_FIRST_WPE
 #define BCHK_FIRST_WPE 5  // measured: 6 / 7 / 8 (spilling) are slower (profiles/r03_help/bench_fwpe*.json)
 #endif
 #define BCHK_SEARCH_ATTR __attribute__((amdgpu_waves_per_eu((TAB && !AN) ? BCHK_FIRST_WPE : 1)))
-#endif
 template <int M, int TMAX, bool TAB, bool AN>
 __global__ void __launch_bounds__(kWaveSize * kWavesPerBlock) BCHK_SEARCH_ATTR
 kaneko_search_kernel(SearchParams p) {
@@ -283,11 +281,6 @@ kaneko_first_kernel(SearchParams p) {
             load_row<M>(p, cw0 + kn, lane, ynext);
             if (!SEL) txnext = tx_prefetch<M>(p, cw0 + kn, lane);
         }
-#if defined(BCHK_FIRST_CUT) && BCHK_FIRST_CUT == 1
-        // experiment builds only (wrong results, timing of the phases): channel loads
-        if (yv[0] + yv[NW - 1] == 12345.0) p.l0[cw] = 0.0;  // keeps the loads
-        continue;
-#endif
         if constexpr (TMAX <= 15) {
             const uint32_t kb = k & ~3u;
             if (k == (uint32_t)__builtin_ctz(todo & (0xFu << kb))) {
@@ -329,18 +322,6 @@ kaneko_first_kernel(SearchParams p) {
             nsel = Geo<M>::N;
             prep_loaded<M, TMAX>(p, col, as, ap, ordl, yv, lane, P);
         }
-#if defined(BCHK_FIRST_CUT) && BCHK_FIRST_CUT == 2
-        ap[lane] = P.asv[0] + (double)P.S0[0] + (double)P.Lo[0];  // + prep (sort, syndromes)
-        continue;
-#endif
-#if defined(BCHK_FIRST_CUT) && BCHK_FIRST_CUT == 3
-        {  // + one wave decode
-            Mask<NW> E;
-            const bool ok = alg_decode_wave<M, TMAX>(ex, lg, P.S0, p.t, lane, E);
-            ap[lane] = P.asv[0] + (ok ? (double)E.w[0] : 0.0);
-        }
-        continue;
-#endif
         SearchState<NW> S;
         init_state<M>(S, p.variant);
         bool bail = false;
@@ -353,10 +334,6 @@ kaneko_first_kernel(SearchParams p) {
         } else {
             first_patterns<M, TMAX>(S, P, p, ex, lg, as, ap, lane, nsel, &bail);
         }
-#if defined(BCHK_FIRST_CUT) && BCHK_FIRST_CUT == 4
-        ap[lane] = S.l0 + (double)(S.done ? 1 : 0) + (double)(bail ? 2 : 0);  // + the first patterns
-        continue;
-#endif
         if (S.done && !bail) {
             if constexpr (SEL) {
                 // the decoded row into the block (the accepted word: a finished codeword
@@ -441,19 +418,11 @@ kaneko_first_kernel(SearchParams p) {
 // 9.9, + 4-chunk claims in the last 60 chunks 81.1-81.6 / 9.8-9.9, 384 slots 81.1 / 9.7;
 // profiles/r04_long/coop_ring*.jsonl). Round 5, with helper workgroups (the ring is also the
 // window of chunks helpers may run ahead): 256 slots 64.2 / 1.57 ms, 512 64.2 / 1.17, 1024
-// 64.3 / 1.07 (profiles/r05_long/help_ring_slots.jsonl). With the decoders' product table
-// (BCHK_LONG_GFMUL, 64 KiB of LDS at m = 8) 1024 slots (123 KiB at m = 8) no longer fit: 512.
-// The decoders' GF arithmetic (m >= 7): 0 = log / exp tables (GfPlain), 1 = the product
-// table (GfMul: no log lookups, ~18 % fewer lookups per test word). Measured (round 6,
-// profiles/r06_long/coop_gfmul_rejected.jsonl): cooperative kernel 5 dB J = 15 64.6 -> 89.8
-// ms, 6 dB J = inf 1.05 -> 1.63 ms. Random byte lookups spread over 64 KiB meet more bank
-// conflicts than sums of two logs into the 1-KiB exp table, where lanes often share a dword
-// (a broadcast), so the product table is an experiment build only (make gm1).
-#ifndef BCHK_LONG_GFMUL
-#define BCHK_LONG_GFMUL 0
-#endif
+// 64.3 / 1.07 (profiles/r05_long/help_ring_slots.jsonl). A whole GF product table for the
+// decoders in place of the log / exp tables was 39 % slower (64.6 -> 89.8 ms, round 6,
+// profiles/r06_long/coop_gfmul_rejected.jsonl) and is gone.
 #ifndef BCHK_LONG_SLOTS
-#define BCHK_LONG_SLOTS (BCHK_LONG_GFMUL ? 512 : 1024)
+#define BCHK_LONG_SLOTS 1024
 #endif
 #ifndef BCHK_LONG_TAIL
 #define BCHK_LONG_TAIL 60
@@ -501,10 +470,9 @@ static_assert(BCHK_COOP_SLOTS <= 64, "ring flags are polled one slot per lane");
 #ifndef BCHK_LONG_GFREP
 #define BCHK_LONG_GFREP 0
 #endif
-static_assert(!(BCHK_LONG_GFREP && BCHK_LONG_GFMUL), "one GF view for the packed decoders");
 template <int M>
 constexpr size_t coop_gf_bytes() {
-    return BCHK_LONG_GFREP ? (size_t)gf_rep_bytes<M>() : BCHK_LONG_GFMUL ? (size_t)gf_mul_bytes<M>() : 0;
+    return BCHK_LONG_GFREP ? (size_t)gf_rep_bytes<M>() : 0;
 }
 template <int M>
 constexpr int coop_waves() { return Geo<M>::NW > 1 ? BCHK_LONG_COOP_WAVES : kCoopWaves; }
@@ -912,13 +880,6 @@ kaneko_coop_kernel(SearchParams p) {
         __syncthreads();  // the packed tables are in LDS
         gf_rep_fill<M>(grep, ex, lg);
     }
-    if constexpr (NW > 1 && BCHK_LONG_GFMUL) {
-        // the product table from HBM (built by the host; L2-resident after the first CU)
-        static_assert(gf_mul_bytes<M>() % 4 == 0, "dwords");
-        const uint32_t *src = reinterpret_cast<const uint32_t *>(p.gfmul);
-        uint32_t *dst = reinterpret_cast<uint32_t *>(grep);
-        for (int i = (int)threadIdx.x; i < gf_mul_bytes<M>() / 4; i += (int)blockDim.x) dst[i] = src[i];
-    }
     double *as = reinterpret_cast<double *>(wbase);
     double *ap = as + NP;
     uint8_t *ordl = wbase + NP * 16;
@@ -948,8 +909,6 @@ kaneko_coop_kernel(SearchParams p) {
         const int lane = lane_o, tt = uni(t_o);
 #if BCHK_LONG_GFREP
         const GfRep<M> gfr{grep, 4 * (lane & 15)};
-#elif BCHK_LONG_GFMUL
-        const GfMul<M> gfr{grep, lg};
 #else
         const GfPlain<M> gfr{ex, lg};
 #endif
@@ -1205,12 +1164,6 @@ kaneko_coop_kernel(SearchParams p) {
                 const bool ready = c + (uint32_t)(kLongClaim - 1) < cons + kLongSlots && b0 < bnd && b0 < capc;
                 if (!r && !ready) {
                     if (++spins > kSpinLimit) {
-#ifdef BCHK_COOP_DEBUG
-                        if (lane == 0)
-                            printf("dec wid %d cw %u claim %u consumed %u bound %llu done %u redo %u/%u next %u\n", wid, cw, c,
-                                   lds_ld(&ctl->consumed), (unsigned long long)lds_ld64(&ctl->bound),
-                                   lds_ld(&ctl->done), lds_ld(&ctl->redo), lds_ld(&ctl->redo_done), lds_ld(&ctl->next));
-#endif
                         flag_fault(p, kFaultCoopRing);
                         break;
                     }
@@ -1400,12 +1353,6 @@ kaneko_coop_kernel(SearchParams p) {
                 const int run = ~rm ? (int)__builtin_ctzll(~rm) : 64;
                 if (run == 0) {
                     if (++spins > kSpinLimit) {  // never expected: fail the codeword, no hang
-#ifdef BCHK_COOP_DEBUG
-                        if (lane == 0)
-                            printf("acc cw %u c %u bound %llu next %u ready[c] %u l0 %g redo %u/%u\n", cw, c,
-                                   (unsigned long long)S.bound, lds_ld(&ctl->next), lds_ld(&ctl->ready[c % kCoopSlots]),
-                                   S.l0, lds_ld(&ctl->redo), lds_ld(&ctl->redo_done));
-#endif
                         if (lane == 0) flag_fault(p, kFaultCoopRing);
                         S.i_end = 64ull * c;
                         S.truncated = true;
@@ -1440,11 +1387,6 @@ kaneko_coop_kernel(SearchParams p) {
                             uint32_t sp = 0;
                             while (lds_ld(&ctl->redo_done) != cc + 1u && ++sp < kSpinLimit) __builtin_amdgcn_s_sleep(1);
                             if (sp >= kSpinLimit) {
-#ifdef BCHK_COOP_DEBUG
-                                if (lane == 0)
-                                    printf("acc dense wait cw %u cc %u redo %u/%u\n", cw, cc, lds_ld(&ctl->redo),
-                                           lds_ld(&ctl->redo_done));
-#endif
                                 if (lane == 0) flag_fault(p, kFaultCoopRing);
                                 S.i_end = base;
                                 S.truncated = true;
@@ -1725,13 +1667,19 @@ static const void *coop_fn() { return reinterpret_cast<const void *>(&kaneko_coo
 
 // kaneko_first_kernel: kFirstPerWave consecutive codewords per wave; its row blocks after
 // the search kernel's LDS layout
+// BCHK_FIRST_FULLSORT in the environment: the full sort without a stats record too
+// (measurements); read once, at the first launch
+static bool first_fullsort() {
+    static const bool on = env_flag("BCHK_FIRST_FULLSORT");
+    return on;
+}
 template <int M, int TMAX>
 static hipError_t launch_first_impl(const SearchParams &p, size_t lds0, hipStream_t s) {
     const uint32_t per_block = kWavesPerBlock * kFirstPerWave;
     const int blocks = (int)((p.count + per_block - 1) / per_block);
     const size_t lds = lds0 + (size_t)kWavesPerBlock * kFirstWaveExtra;
     if constexpr (first_sel_capable<M, TMAX>()) {
-        if (!p.st && !getenv("BCHK_FIRST_FULLSORT")) {
+        if (!p.st && !first_fullsort()) {
             hipLaunchKernelGGL((kaneko_first_kernel<M, TMAX, true>), dim3(blocks > 0 ? blocks : 1),
                                dim3(kWaveSize * kWavesPerBlock), lds, s, p);
             return hipGetLastError();
@@ -1746,12 +1694,8 @@ static hipError_t launch_first_impl(const SearchParams &p, size_t lds0, hipStrea
 bool select_first_long(int m, int t, FastFn *out) {
 #define BCHK_FIRST(MM, TT) \
     if (m == MM && t <= TT) { *out = &launch_first_impl<MM, TT>; return true; }
-#if defined(BCHK_ISA_ONLY) && BCHK_ISA_ONLY == 8
-    BCHK_FIRST(8, 15)
-#elif !defined(BCHK_ISA_ONLY)
     BCHK_FIRST(7, 8) BCHK_FIRST(7, 16) BCHK_FIRST(7, 32)
     BCHK_FIRST(8, 15) BCHK_FIRST(8, 16) BCHK_FIRST(8, 32)
-#endif
 #undef BCHK_FIRST
     return false;
 }
@@ -1783,7 +1727,6 @@ static KernelSet make_set() {
     }
     k.coop_threads = kWaveSize * coop_waves<M>();
     k.long_job_bytes = Geo<M>::NW > 1 ? sizeof(JobData<M, TMAX>) : 0;
-    k.gfmul = Geo<M>::NW > 1 && BCHK_LONG_GFMUL;
     k.coop_bytes = coop;
     k.alg = &launch_alg_impl<M, TMAX>;
     k.tmax = TMAX;
@@ -1795,11 +1738,6 @@ static KernelSet make_set() {
 bool select_kernels(int m, int t, KernelSet *out) {
 #define BCHK_TRY(MM, TT) \
     if (m == MM && t <= TT) { *out = make_set<MM, TT>(); return true; }
-#if defined(BCHK_ISA_ONLY) && BCHK_ISA_ONLY == 8  // ISA inspection builds: one code's kernels only
-    BCHK_TRY(8, 15)
-#elif defined(BCHK_ISA_ONLY)
-    BCHK_TRY(6, 6)
-#else
     BCHK_TRY(2, 1)
     BCHK_TRY(3, 3)
     BCHK_TRY(4, 2) BCHK_TRY(4, 7)
@@ -1807,7 +1745,6 @@ bool select_kernels(int m, int t, KernelSet *out) {
     BCHK_TRY(6, 6) BCHK_TRY(6, 12) BCHK_TRY(6, 31)
     BCHK_TRY(7, 8) BCHK_TRY(7, 16) BCHK_TRY(7, 32)
     BCHK_TRY(8, 15) BCHK_TRY(8, 16) BCHK_TRY(8, 32)
-#endif
 #undef BCHK_TRY
     return false;
 }
@@ -1830,7 +1767,7 @@ hipError_t launch_count(int n, const uint8_t *tx, const uint8_t *res, const bchk
     // (1024 blocks: 43.6 us at 2^20 x 63 vs 67.8 us with one block per 256 rows,
     // profiles/r01_long/count_grid.jsonl)
     // (BCHK_COUNT_GRID overrides the cap for experiments)
-    static const int cap = getenv("BCHK_COUNT_GRID") ? atoi(getenv("BCHK_COUNT_GRID")) : 1024;
+    static const int cap = [] { int c = 1024; env_int("BCHK_COUNT_GRID", &c, INT_MIN, INT_MAX); return c; }();
     const int grid = (int)((B + 255) / 256) < cap ? (int)((B + 255) / 256) : cap;
     unsigned long long *o = reinterpret_cast<unsigned long long *>(out6);
     switch (n) {

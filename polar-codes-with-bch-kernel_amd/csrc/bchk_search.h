@@ -13,13 +13,9 @@
 #include "bchk_core.h"
 #include "bchk_launch.h"
 
-// Tuning knobs (experiment builds override them): chunks per syndrome-table lookup group,
-// and calcL terms whose LDS loads are issued together.
+// Tuning knob (experiment builds override it): chunks per syndrome-table lookup group.
 #ifndef BCHK_TAB_GROUP
 #define BCHK_TAB_GROUP 1
-#endif
-#ifndef BCHK_LSUM_BATCH
-#define BCHK_LSUM_BATCH 8
 #endif
 
 namespace bchk {
@@ -37,10 +33,7 @@ struct Smem {
 constexpr int kCoopWaves = BCHK_COOP_WAVES;  // waves that share one heavy codeword (1024 threads)
 // long codes: test patterns decoded one at a time by the whole wave before the 64-pattern
 // chunks (search_codeword)
-#ifndef BCHK_SEQ_PATTERNS
-#define BCHK_SEQ_PATTERNS 4
-#endif
-constexpr int kSeqPatterns = BCHK_SEQ_PATTERNS;
+constexpr int kSeqPatterns = 4;
 static_assert(kSeqPatterns >= 1 && kSeqPatterns <= 64, "sequential patterns lie in chunk 0");
 
 // ------------------------------------------------------- per-codeword prep
@@ -461,10 +454,10 @@ __device__ __forceinline__ void decode_chunks(const Prep<M, TMAX> &P, uint64_t b
         l[g] = 0.0;
         if (ok[g]) {
             m[g] = mask_popc<NW>(diff[g]);
-            if constexpr (NW == 1 && BCHK_LSUM_BATCH > 0) {
+            if constexpr (NW == 1) {
                 // calcL in index order (:69-77): the first KL terms' LDS loads are issued
                 // together, then summed in order (one LDS round trip instead of one per term)
-                constexpr int KL = BCHK_LSUM_BATCH > 0 ? BCHK_LSUM_BATCH : 1;
+                constexpr int KL = 8;
                 double v[KL];
                 uint64_t d = diff[g].w[0];
 #pragma unroll

@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "bchk.h"
+#include "bchk_env.h"
 #include "bchk_philox.h"
 
 namespace bchk {
@@ -252,10 +253,8 @@ struct BecScratch {
 // patterns per lane: BCHK_BEC_RUN in the environment (1..kRunMax), else sized so that a full
 // launch is about kTargetLanes lanes. Counts do not depend on it.
 uint32_t pick_run(uint64_t n) {
-    if (const char *e = getenv("BCHK_BEC_RUN")) {
-        const long v = atol(e);
-        if (v >= 1) return (uint32_t)std::min<long>(v, (long)kRunMax);
-    }
+    int v = 0;
+    if (bchk::env_int("BCHK_BEC_RUN", &v, 0, (int)kRunMax) && v >= 1) return (uint32_t)v;
     const uint64_t r = (n + kTargetLanes - 1) / kTargetLanes;
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>(r, 1), kRunMax);
 }

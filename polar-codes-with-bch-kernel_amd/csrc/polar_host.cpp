@@ -11,6 +11,8 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cfloat>
+#include <climits>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -22,6 +24,7 @@
 #include <vector>
 
 #include "bchk.h"
+#include "bchk_env.h"
 #include "polar_device.h"
 
 using namespace bchk;
@@ -411,6 +414,16 @@ void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
 
 extern "C" {
 
+// a persistent kernel's grid: per_cu workgroups on each CU, or BCHK_POLAR_GRID workgroups
+// (experiments); BCHK_POLAR_DEBUG prints the choice
+static int polar_grid(const char *who, const bchk_polar *c, size_t lds, int per_cu, int cus) {
+    int grid = per_cu * cus;
+    env_int("BCHK_POLAR_GRID", &grid, 1, INT_MAX);
+    if (env_flag("BCHK_POLAR_DEBUG"))
+        fprintf(stderr, "%s: U=%d L=%d lds=%zu per_cu=%d CUs=%d grid=%d\n", who, c->U, c->L, lds, per_cu, cus, grid);
+    return grid;
+}
+
 int bchk_polar_create(const char *spec, int list_size, int device, bchk_polar **out) {
     return bchk_polar_create_kdir(spec, nullptr, list_size, device, out);
 }
@@ -436,11 +449,11 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         // larger than the trellis limit (or from BCHK_POLAR_ML up) from the exact
         // ordered-statistics search
         int tmin = 16, mlmin = kPolarMaxTrellisKernel + 1;
-        if (const char *e = getenv("BCHK_POLAR_TRELLIS")) tmin = std::max(2, atoi(e));
-        if (const char *e = getenv("BCHK_POLAR_ML")) mlmin = std::max(2, atoi(e));
+        env_int("BCHK_POLAR_TRELLIS", &tmin, 2, INT_MAX);
+        env_int("BCHK_POLAR_ML", &mlmin, 2, INT_MAX);
         // the search's round guard (a finite tree: never reached in practice; tests lower it)
-        m.ml_rounds = kMlRoundsDefault;
-        if (const char *e = getenv("BCHK_POLAR_ML_ROUNDS")) m.ml_rounds = (uint32_t)std::max(1L, atol(e));
+        int rounds = 0;
+        m.ml_rounds = env_int("BCHK_POLAR_ML_ROUNDS", &rounds, 1, INT_MAX) ? (uint32_t)rounds : kMlRoundsDefault;
         m.any_ml = 0;
         m.tstates = 0;
         c->tbase.assign((size_t)nl * kPolarMaxKernel, 0u);
@@ -533,18 +546,14 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         per_cu = 1;
         (void)hipGetLastError();
     }
-    c->grid = per_cu * prop.multiProcessorCount;
-    if (const char *g = getenv("BCHK_POLAR_GRID")) c->grid = std::max(1, atoi(g));
+    c->grid = polar_grid("bchk_polar", c, c->lds, per_cu, prop.multiProcessorCount);
     // codes with search layers: launches of at most ~50 ms (BCHK_POLAR_BUDGET_MS, 0 = one
     // launch per call), so no launch holds the GPU for seconds
     if (c->mixed && c->mp.any_ml) {
         double ms = 50.0;
-        if (const char *b = getenv("BCHK_POLAR_BUDGET_MS")) ms = std::max(0.0, atof(b));
+        env_double("BCHK_POLAR_BUDGET_MS", &ms, 0.0, DBL_MAX);
         c->budget_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
     }
-    if (getenv("BCHK_POLAR_DEBUG"))
-        fprintf(stderr, "bchk_polar: U=%d L=%d lds=%zu per_cu=%d CUs=%d grid=%d\n", c->U, c->L, c->lds, per_cu,
-                prop.multiProcessorCount, c->grid);
     *out = c;
     return 0;
 }
@@ -660,7 +669,7 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         m.unfinished = (uint32_t *)c->unfinished.p;  // two words: unfinished, progress
         m.progress = m.unfinished + 1;
         m.budget = c->budget_ticks;
-        m.no_mid = getenv("BCHK_POLAR_NO_MID") ? 1 : 0;
+        m.no_mid = env_flag("BCHK_POLAR_NO_MID") ? 1 : 0;  // per call: tests toggle it on a live context
         for (uint64_t launch = 0;; ++launch) {
             PHIP_TRY(hipMemsetAsync(c->unfinished.p, 0, 8, s));
             PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
@@ -955,12 +964,8 @@ static int genie_setup(bchk_polar *c) {
         cus = 1;
         (void)hipGetLastError();
     }
-    int grid = per_cu * cus;
-    if (const char *e = getenv("BCHK_POLAR_GRID")) grid = std::max(1, atoi(e));
-    if (getenv("BCHK_POLAR_DEBUG"))
-        fprintf(stderr, "bchk_polar genie: U=%d lds=%zu per_cu=%d CUs=%d grid=%d\n", c->U, lds, per_cu, cus, grid);
     c->genie_lds = lds;
-    c->genie_grid = grid;
+    c->genie_grid = polar_grid("bchk_polar genie", c, lds, per_cu, cus);
     return 0;
 }
 

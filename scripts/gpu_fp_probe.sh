@@ -12,7 +12,7 @@ import sys; sys.path.insert(0,'tests')
 from bchk_pkg import load
 F=load(); d=F.KanekoKernelProcessor(6,6,J=15); d8=F.KanekoKernelProcessor(8,15,J=15)" > $OUT/${TAG}_grid.log 2>&1
 rc=$?; cat $OUT/${TAG}_grid.log | grep bchk; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 200 env BCHK_LIB=$ROOT/polar-codes-with-bch-kernel_amd/lib/libbchk_xanprof.so python scripts/an_diag.py 1 > $OUT/${TAG}_anprof.jsonl 2> $OUT/${TAG}_anprof.err
+timeout -k 10 200 env BCHK_LIB=$ROOT/polar-codes-with-bch-kernel_amd/lib/libbchk_anprof.so python scripts/an_diag.py 1 > $OUT/${TAG}_anprof.jsonl 2> $OUT/${TAG}_anprof.err
 rc=$?; echo "anprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
 python -c "
 import json,sys
