@@ -272,8 +272,14 @@ int bchk_syndrome_table_query(int m, int t, const uint32_t *synd, size_t N, uint
 /* Size of that table: distinct keys, bytes, longest probe sequence (buckets). */
 int bchk_syndrome_table_info(int m, int t, uint64_t *keys, uint64_t *bytes, uint32_t *max_probe);
 
-/* ---- SC-list decoding of polar codes (the reference's vendored library, never built by
- * the reference itself: headers/external/MixedKernelListDecoder.h:10-42). */
+/* ---- SC-list decoding of polar codes (the reference's vendored library, which its own
+ * CMake target does not build: headers/external/MixedKernelListDecoder.h:10-42). Pinned to
+ * that library compiled as it stands, for kernels below 64: decode, encode and the kernel
+ * LLRs are compared bit for bit with its recorded outputs (tests/golden/polar_ref_*.txt.gz,
+ * tests/test_polar_reference.py). LLR sign at this boundary: negative favours bit 1, as the
+ * reference's code reads it (MixedKernelListDecoder.cpp:80, :114; its header comment at :36
+ * says the opposite and is not what the code does). The 64 x 64 kernel's LLRs have no
+ * reference to compare with (TrellisKernelProcessor.cpp:71-72 refuses the size). */
 typedef struct bchk_polar bchk_polar;
 /* Replaces CMixedKernelListDecoder(std::istream& Spec, unsigned ListSize)
  * (out/external/MixedKernelListDecoder.cpp:9): spec is the text of the reference's code

@@ -6,7 +6,13 @@ oracle/_ref/ref_golden and oracle/_ref/kaneko are compiled by oracle/Makefile fr
 unmodified sources under /root/reference (this container only). The fixtures are data
 (inputs and the reference's outputs); no reference source text is stored.
 
-    make -C oracle ref && python oracle/make_golden.py
+    make -C oracle ref && python oracle/make_golden.py            # the Kaneko fixtures
+    make -C oracle ref && python oracle/make_golden.py polar      # the polar_ref_* fixtures
+
+The `polar` sub-command needs the product library built as well (kernel matrices come from
+its bchk_kernel_ebch): oracle/_ref/polar_ref is our driver (oracle/polar_ref.cpp) linked with
+the reference's vendored polar library. The polar_ref_*.txt.gz format is described in
+tests/polar_ref_lib.py.
 
 Fixture formats (gzip text, one record per line):
   vectors_*.txt.gz   '# code n k t m gsize G seed S snr X count C' header, then per word
@@ -44,7 +50,7 @@ def run(args, cwd=None):
     return subprocess.run(args, check=True, capture_output=True, text=True, cwd=cwd).stdout
 
 
-def main():
+def kaneko():
     if not os.path.exists(os.path.join(REF, "ref_golden")):
         sys.exit("build the reference first: make -C oracle ref")
     os.makedirs(GOLD, exist_ok=True)
@@ -83,6 +89,112 @@ def main():
         with open(os.path.join(tmp, "out.csv")) as src, open(os.path.join(GOLD, name), "w") as dst:
             dst.write(src.read())
         print(name)
+
+
+# ------------------------------------------------------------------------ polar fixtures
+# Arikan codes: n, K, dynamic frozen, punctured, list sizes (test_polar_sclist's codes; for
+# n = 3, 4 the lists of 8 and 32 are the full 2^K lists). Eb/N0 = 1.0 + 0.25 n dB.
+POLAR_LISTS = (1, 2, 4, 8, 32)
+POLAR_ARIKAN = [(3, 3, 0, ()), (4, 5, 0, ()), (5, 16, 3, ()), (6, 32, 5, (1, 7)),
+                (8, 128, 12, (0, 3, 17, 40))]
+# matrix-kernel codes: layers (outermost first), K, dynamic frozen, punctured
+POLAR_MIXED = [(("k4", "A"), 4, 0, ()), (("bch8", "A"), 8, 2, ()), (("bch16", "A"), 16, 2, ()),
+               (("bch32f",), 16, 2, ()), (("bch32f", "A"), 32, 2, ())]
+# bch32f: the 32 x 32 extended-BCH kernel in field-element column order (bchk_kernel_field_order,
+# the reference's swapColumns). As bchk_kernel_ebch leaves it its trellis has 2^13 states, over
+# the GPU decoder's 2^12: that form is pinned by its trellis fixture (trellis_bch32) alone.
+POLAR_MIXED_LISTS = (1, 4, 8)
+POLAR_WORDS = 32
+
+
+def polar():
+    import tempfile
+
+    import numpy as np
+
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import polar_ref_lib as R
+    from bchk_pkg import load
+    from polar_lib import arikan_spec, awgn_llr
+    from test_polar_mixed import KERNELS, mixed_spec
+
+    if not os.path.exists(R.POLAR_REF):
+        sys.exit("build the reference first: make -C oracle ref")
+    F = load()
+    kern = {"k4": KERNELS["k4"], "bch8": F.kernel_ebch(3), "bch16": F.kernel_ebch(4), "bch32": F.kernel_ebch(5),
+            "bch32f": F.kernel_field_order(5, F.kernel_ebch(5))}
+    os.makedirs(GOLD, exist_ok=True)
+    for p in R.fixture_files("code") + R.fixture_files("trellis"):
+        os.remove(p)
+
+    def emit(fx):
+        with tempfile.TemporaryDirectory() as d:
+            out = R.regenerate(fx, d)
+        path = os.path.join(GOLD, f"polar_ref_{fx.name}.txt.gz")
+        out.save(path)
+        print(os.path.basename(path), os.path.getsize(path))
+
+    def code_fixture(name, spec, kernels, lists, snr, seed, llr_map=None, words=POLAR_WORDS):
+        """Inputs of one code: random information words, their codewords (by the reference's own
+        encoder) over BPSK / AWGN at Eb/N0 snr."""
+        fx = R.Fixture(name, [f"polar_ref fixture: code {name}, Eb/N0 {snr:g} dB, seed {seed}; recorded outputs of "
+                              "the reference's vendored decoder and encoder (oracle/make_golden.py polar)"])
+        fx.add("spec", [], spec.rstrip("\n").split("\n"))
+        for kname in kernels:
+            fx.add("kernel", [f"{kname}.txt", len(kern[kname])], [" ".join(str(int(v)) for v in r) for r in kern[kname]])
+        hdr = [int(v) for v in spec.split()[:6]]
+        N, K = hdr[0], hdr[1]
+        rng = np.random.default_rng(seed)
+        dec_info = rng.integers(0, 2, (words, K)).astype(np.uint8)
+        enc_info = rng.integers(0, 2, (30, K)).astype(np.uint8)
+        with tempfile.TemporaryDirectory() as d:
+            fx.write_kernels(d)
+            with open(os.path.join(d, "spec.txt"), "w") as f:
+                f.write(spec)
+            cw = np.array([R.bits(r) for r in R.run_ref(["encode", "spec.txt"], [R.bits_row(w) for w in dec_info], d)])
+        llr = awgn_llr(cw, snr, K / N, seed=seed + 1)
+        if llr_map:
+            llr = llr_map(llr)
+        fx.add("llr", [], [R.hex_row(r) for r in llr])
+        for L in lists:
+            fx.add("decode", [L], [])
+        fx.add("info", [], [R.bits_row(w) for w in enc_info])
+        fx.add("encode", [], [])
+        return fx
+
+    for n, K, dyn, punct in POLAR_ARIKAN:
+        emit(code_fixture(f"arikan_n{n}", arikan_spec(n, K, dyn=dyn, punct=punct, seed=n), (), POLAR_LISTS,
+                          1.0 + 0.25 * n, seed=n * 7))
+    # equal metrics and exact zeros: LLRs rounded to multiples of 4 (|llr| < 2 becomes 0)
+    emit(code_fixture("arikan_n7_ties", arikan_spec(7, 64, dyn=4, seed=77), (), (8,), 1.0, seed=77,
+                      llr_map=lambda x: (4.0 * np.round(x / 4.0)).astype(np.float32), words=48))
+    for layers, K, dyn, punct in POLAR_MIXED:
+        spec = mixed_spec(layers, K, dyn, punct, seed=len(layers) * 11 + K)  # sizes by test_polar_mixed's names
+        U = int(np.prod([2 if l == "A" else len(kern[l]) for l in layers]))
+        nbits = int(round(np.log2(U)))
+        emit(code_fixture("mixed_" + "_".join(layers), spec, [l for l in layers if l != "A"], POLAR_MIXED_LISTS,
+                          1.0 + 0.25 * nbits, seed=U + K))
+    for kname in ("bch8", "bch16", "bch32", "bch32f"):
+        l = len(kern[kname])
+        rng = np.random.default_rng(l + len(kname))
+        fx = R.Fixture(f"trellis_{kname}", [f"polar_ref fixture: CTrellisKernelProcessor::GetLLRs of the {l} x {l} "
+                                            "extended-BCH kernel, every phase (oracle/make_golden.py polar)"])
+        fx.add("kernel", [f"{kname}.txt", l], [" ".join(str(int(v)) for v in r) for r in kern[kname]])
+        fx.add("trellis_in", [], [R.bits_row(rng.integers(0, 2, l)) + " " +
+                                  R.hex_row(rng.normal(0, 1.5, l).astype(np.float32)) for _ in range(16)])
+        fx.add("trellis_out", [], [])
+        emit(fx)
+
+
+def main():
+    import argparse
+    ap = argparse.ArgumentParser(
+        description="Regenerate tests/golden/ by running the compiled reference (oracle/_ref/, built by "
+                    "`make -C oracle ref`).",
+        epilog="`python oracle/make_golden.py` rewrites the Kaneko fixtures; `python oracle/make_golden.py polar` "
+               "rewrites every polar_ref_*.txt.gz (SC-list decoder, encoder, trellis kernel processor).")
+    ap.add_argument("what", nargs="?", default="kaneko", choices=["kaneko", "polar"])
+    {"kaneko": kaneko, "polar": polar}[ap.parse_args().what]()
 
 
 if __name__ == "__main__":

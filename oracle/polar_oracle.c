@@ -3,7 +3,7 @@
  * oracle/build/libpolar_oracle.so and loaded only by tests/.
  *
  * Follows (paths in the reference repo; the library under out/external is vendored and
- * never built by the reference itself):
+ * not built by the reference's own CMake target):
  *   spec format, encoder, info extraction  out/external/MixedKernelEncoder.cpp:7-98, :142-177, :209-238
  *   dynamic-freezing masks                 out/external/KernelListEngine.cpp:6-39
  *   list decoder                           out/external/MixedKernelListDecoder.cpp:61-185, :211-268
@@ -19,9 +19,18 @@
  * commutes with adding a constant under round-to-nearest, so the minimum is the trellis's
  * bit for bit.
  *
- * PARITY UNPINNED: the vendored library needs GSL, Windows.h, MSVC-only constructs and 10
- * headers absent from the reference, and no fixtures exist; this file is
- * checked by properties in tests/test_polar_oracle.py.
+ * PINNED, kernels below 64: oracle/Makefile compiles the vendored library as it stands (our
+ * shim headers for GSL and MSVC, oracle/vendored_shim/) with our driver oracle/polar_ref.cpp
+ * into oracle/_ref/polar_ref; `oracle/make_golden.py polar` records its decoder, encoder and
+ * trellis processor in tests/golden/polar_ref_{arikan,mixed,trellis}_*.txt.gz, and
+ * tests/test_polar_reference.py compares this file with them bit for bit: list count,
+ * information vectors, codewords, list order, f32 metric bits, and the kernel LLRs of
+ * enum_ / trellis_ / ml_minsum_llr at every phase. As first compared, this file agreed with
+ * the reference on every fixture; nothing had to change.
+ * STILL UNPINNED: ml_minsum_llr on the 64 x 64 kernel -- the reference's trellis processor
+ * refuses sizes >= 64 (TrellisKernelProcessor.cpp:71-72), so no reference output exists; it
+ * is checked against this file's own enumeration and trellis (tests/test_polar_ml.py) and,
+ * for sizes <= 32, against the reference through the fixtures above.
  */
 #include "polar_oracle.h"
 

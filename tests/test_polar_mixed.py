@@ -1,9 +1,11 @@
 """SC-list decoding over MIXED kernels on the GPU (csrc/polar_mixed.hip): Arikan layers and
 matrix kernels (the reference's kernel files, Kernel.cpp:93-107 -- e.g. BCH-derived kernels),
 whose kernel LLRs are the trellis min-sum of out/external/TrellisKernelProcessor.cpp:234-294.
-Bit for bit against the C restatement (oracle/polar_oracle.c; its parity is unpinned, as
-for the Arikan decoder -- SURVEY.md §8c): list counts, information vectors, codewords, f32
-path metrics."""
+Bit for bit against the C restatement (oracle/polar_oracle.c): list counts, information
+vectors, codewords, f32 path metrics. For kernels up to 32 x 32 that restatement, and the GPU
+decoder directly, are pinned to the compiled vendored library by tests/test_polar_reference.py
+(tests/golden/polar_ref_mixed_*, polar_ref_trellis_*); kernels of size >= 64 stay unpinned,
+the reference's trellis processor refuses them (TrellisKernelProcessor.cpp:71-72)."""
 import os
 
 import numpy as np

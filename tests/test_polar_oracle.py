@@ -1,6 +1,7 @@
 """The C restatement of the vendored SC-list decoder (oracle/polar_oracle.c) checked by
-properties -- its parity is unpinned: the vendored library cannot be built here and ships
-no fixtures.
+properties. Its parity with the vendored library itself is pinned separately, by
+tests/test_polar_reference.py against tests/golden/polar_ref_*.txt.gz (the compiled library's
+recorded outputs, kernels below 64); the properties here also cover what no fixture can.
 
 * encoder / information extraction are inverse (MixedKernelEncoder.cpp:142-177, :209-238);
 * noiseless words decode to themselves at metric 0, for every list size;

@@ -5,8 +5,8 @@ vectors, codewords, path metrics (f32 bits) and list counts, bit for bit.
 Codes are length-2^n Arikan polar codes in the reference's specification format
 (out/external/MixedKernelEncoder.cpp:7-98) with static and dynamic frozen symbols and
 puncturing; LLRs come from BPSK over AWGN as in the reference's simulator
-(headers/external/Modem.h:64-78). The oracle's own parity is unpinned (no fixtures ship
-with the vendored library) -- see tests/test_polar_oracle.py.
+(headers/external/Modem.h:64-78). The oracle itself, and the GPU decoder directly, are pinned
+to the compiled vendored library by tests/test_polar_reference.py (tests/golden/polar_ref_*).
 """
 import numpy as np
 import pytest
