@@ -446,10 +446,18 @@ int bchk_kernel_bec_behaviour(const uint8_t *K, int l, int w_lo, int w_hi, int d
  * patterns of weight pattern_weight, in rank / sample order (room for min(C(l, w), samples)). */
 int bchk_kernel_bec_sample(const uint8_t *K, int l, uint64_t samples, uint64_t seed, int device, uint64_t *unc,
                            uint64_t *tried, uint8_t *exact, int pattern_weight, uint64_t *patterns);
-/* CBECCapacityEvaluator::GetSubchannelCapacity (CapacityEvaluator.cpp:124-140) restated
- * (the reference's evaluator is never built: parity unpinned): the capacity of phase `phase`
- * over a BEC of capacity C, 1 - sum_w counts[phase][w] P^w C^(l - w) with P = 1 - C, by the
- * same Horner rule in double; 1 - counts[phase][l] at C = 0. Host only. */
+/* CBECCapacityEvaluator::GetSubchannelCapacity (CapacityEvaluator.cpp:124-140) restated and
+ * pinned to the compiled evaluator (tests/golden/polar_ref_capacity_*.txt.gz: equal bits on
+ * every recorded row with C > 0): the capacity of phase `phase` over a BEC of capacity C,
+ * 1 - sum_w counts[phase][w] P^w C^(l - w) with P = 1 - C, by the same Horner rule in
+ * S = P / C in double. Host only.
+ * Divergence: at C = 0 the reference divides by zero and returns NaN; this returns the
+ * polynomial's value 1 - counts[phase][l].
+ * Domain: the rule is accurate to a few 2^-53 ABSOLUTE, so only while the capacity it returns is
+ * well above 1e-16, in practice for C near 1/2. For small C the result is rounding noise of
+ * either sign (l = 4, C = 1e-5: -2.2e-16 for a true 1e-20), then -inf or NaN once S^l overflows
+ * or pow(C, l) underflows (l = 16: NaN from C = 1e-40; l = 32: -inf at 1e-10) -- reproduced here
+ * bit for bit. bchk_polar_design_bec does not use it for matrix layers. */
 int bchk_kernel_bec_capacity(const uint64_t *counts, int l, int phase, double C, double *out);
 /* A kernel file in the reference's format (Kernel.cpp:93-134): the size, the matrix and, when
  * counts is given, the BEC section CBECCapacityEvaluator's constructor parses -- channel id 3
@@ -464,7 +472,11 @@ int bchk_kernel_write_file(const char *path, const uint8_t *K, int l, const uint
  * tables need no device. Symbol i has mixed-radix digits (a_0 .. a_{n-1}), a_0 most
  * significant; layer 0 faces the channel (MixedKernelEncoder.cpp:161-173), so its capacity is
  * T_{n-1,a_{n-1}}( .. T_{1,a_1}(T_{0,a_0}(capacity))), T of an "A" layer being C^2 and
- * 2C - C^2 (Kernel.cpp:70-75). The K largest capacities carry information, ties going to
+ * 2C - C^2 (Kernel.cpp:70-75), and of a matrix layer sum_w (C(l, w) - counts[a][w]) P^w C^(l-w),
+ * the sum over correctable patterns: the same polynomial as bchk_kernel_bec_capacity's, but
+ * with no negative term, so that it keeps its relative accuracy ((5 l + 4) 2^-53) for the
+ * capacities far below 1e-16 that inner layers see (a sampled table's difference is clamped
+ * at 0); every capacity is finite and in [0, 1]. The K largest capacities carry information, ties going to
  * the higher index. cap (may be NULL) receives the U capacities; spec receives the text
  * "U K 0 n 0 0", the layer line and "1 f" per frozen symbol, ascending (no shortening,
  * puncturing or dynamic freezing). *needed = the bytes the text takes with its terminator

@@ -24,9 +24,11 @@
  * and source are absent from the reference; the objective restated here is
  * that of CTrellisKernelProcessor, the processor CMatrixBinaryKernel::GetProcessor(0)
  * returns (out/external/Kernel.cpp:276-281) and the one the earlier exhaustive swapColumns
- * (root bchCoder.cpp:413-475) used. The vendored library cannot be built here, so these
- * counts are parity unpinned; kor_trellis_counts' LLRs are checked against an independent
- * coset enumeration in tests/test_kernel_search.py.
+ * (root bchCoder.cpp:413-475) used. kor_trellis_counts is pinned to that processor compiled
+ * with -DOPERATION_COUNTING (oracle/_ref/polar_ref counts): tests/golden/polar_ref_counts_*.txt.gz,
+ * tests/test_kernel_search_reference.py; its LLRs are checked against an independent coset
+ * enumeration in tests/test_kernel_search.py. The acceptance rule and the candidate draws of
+ * the search stay unpinned (root bchCoder.cpp cannot be built).
  */
 #include <stdint.h>
 #include <stdlib.h>

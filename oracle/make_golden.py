@@ -124,7 +124,7 @@ def polar():
     kern = {"k4": KERNELS["k4"], "bch8": F.kernel_ebch(3), "bch16": F.kernel_ebch(4), "bch32": F.kernel_ebch(5),
             "bch32f": F.kernel_field_order(5, F.kernel_ebch(5))}
     os.makedirs(GOLD, exist_ok=True)
-    for p in R.fixture_files("code") + R.fixture_files("trellis"):
+    for p in sum((R.fixture_files(k) for k in ("code", "trellis", "counts", "capacity")), []):
         os.remove(p)
 
     def emit(fx):
@@ -184,6 +184,93 @@ def polar():
                                   R.hex_row(rng.normal(0, 1.5, l).astype(np.float32)) for _ in range(16)])
         fx.add("trellis_out", [], [])
         emit(fx)
+    polar_counts(F, kern, emit)
+    polar_capacity(F, emit)
+
+
+# The column search's score (root bchCoder.cpp:641-653): SumCount / CmpCount growth over GetLLRs
+# at every phase. Kernels: the extended-BCH kernels as built and in field-element order, Kronecker
+# powers of the Arikan kernel, zero span (identity) and maximal span (identity, columns reversed),
+# random invertible kernels of sizes that are no power of two, and the field-ordered 16 x 16
+# kernel under five L.U column maps (the all-zero code, the all-one code, three seeded ones).
+COUNT_RANDOM = (3, 5, 6, 7, 12)
+COUNT_LU_CODES = (0, (1 << 12) - 1) + tuple(int(c) for c in __import__("numpy").random.default_rng(16).choice((1 << 12) - 2, 3, replace=False) + 1)
+
+
+def polar_counts(F, kern, emit):
+    import numpy as np
+
+    import polar_ref_lib as R
+    from test_kernel_search import llrs_like_reference, o_perm, rand_invertible
+
+    F2 = np.array([[1, 0], [1, 1]], np.uint8)
+    ks = {}
+    for power in (2, 3, 4, 5):
+        K = F.kernel_ebch(power)
+        ks[f"bch{1 << power}"] = K
+        ks[f"bch{1 << power}f"] = F.kernel_field_order(power, K)
+    K = np.ones((1, 1), np.uint8)
+    for k in (1, 2, 3, 4):
+        K = np.kron(K, F2)
+        ks[f"kron{k}"] = K
+    ks["id8"] = np.eye(8, dtype=np.uint8)
+    ks["rev8"] = np.eye(8, dtype=np.uint8)[:, ::-1]
+    for l in COUNT_RANDOM:
+        ks[f"rand{l}"] = rand_invertible(l, np.random.default_rng(1000 + l))
+    for code in COUNT_LU_CODES:
+        ks[f"bch16f_lu{code}"] = ks["bch16f"][:, o_perm(4, code)]
+    refused = []
+    for name, K in ks.items():
+        l = len(K)
+        fx = R.Fixture(f"counts_{name}", [f"polar_ref fixture: SumCount / CmpCount of CTrellisKernelProcessor::GetLLRs over every "
+                                          f"phase of the {l} x {l} kernel {name}, zero known inputs (oracle/make_golden.py polar)"])
+        fx.add("kernel", [f"{name}.txt", l], [" ".join(str(int(v)) for v in r) for r in K])
+        if "_lu" in name:
+            fx.add("lu_code", [name.split("_lu")[1]], [])
+        rows = [llrs_like_reference(l, 31 * l + s) for s in range(3)]  # (rand() % 10) - 5: exact zeros occur
+        rows += [np.zeros(l, np.float32), -(1 + np.arange(l) % 5).astype(np.float32)]
+        fx.add("counts_in", [], [R.hex_row(r) for r in rows])
+        fx.add("counts_out", [], [])
+        try:
+            emit(fx)
+        except RuntimeError as e:
+            refused.append((name, str(e)))
+    print("kernels the reference refused:", refused or "none")
+
+
+CAPACITIES = [round(0.05 * i, 2) for i in range(1, 20)] + [1 - 1e-9, 1.0, 1e-3, 1e-5, 1e-10, 1e-20, 1e-40, 0.0]
+
+
+def polar_capacity(F, emit):
+    """The library's kernel-file reader and BEC capacity evaluator on files bchk_kernel_write_file
+    wrote (host only): exact tables of the 4 x 4 and 16 x 16 extended-BCH kernels from the numpy
+    checker, and of the 5-fold Kronecker power of the Arikan kernel from its closed form."""
+    import tempfile
+
+    import numpy as np
+
+    import polar_ref_lib as R
+    from test_kernel_bec import kron_power_table
+    from test_polar_design import F2, table_of
+
+    K5 = F2
+    for _ in range(4):
+        K5 = np.kron(K5, F2)
+    cases = [("bch4", "k4t.txt", F.kernel_ebch(2), None), ("bch16", "e16t.txt", F.kernel_ebch(4), None),
+             ("kron5", "f32t.txt", K5, np.array(kron_power_table(5), np.uint64))]
+    for name, fname, K, tab in cases:
+        tab = table_of(K) if tab is None else tab
+        with tempfile.TemporaryDirectory() as d:
+            F.write_kernel_file(os.path.join(d, fname), K, tab)
+            text = open(os.path.join(d, fname)).read()
+        assert text.endswith("\n")
+        fx = R.Fixture(f"capacity_{name}", [f"polar_ref fixture: CMatrixBinaryKernel's reader and CBECCapacityEvaluator::"
+                                            f"GetSubchannelCapacity on the file bchk_kernel_write_file wrote for {name} "
+                                            "(oracle/make_golden.py polar)"])
+        fx.add("kernel_file", [fname], text[:-1].split("\n"))
+        fx.add("capacity_in", [], [R.hex64(c) for c in CAPACITIES])
+        fx.add("capacity_out", [], [])
+        emit(fx)
 
 
 def main():
@@ -192,7 +279,8 @@ def main():
         description="Regenerate tests/golden/ by running the compiled reference (oracle/_ref/, built by "
                     "`make -C oracle ref`).",
         epilog="`python oracle/make_golden.py` rewrites the Kaneko fixtures; `python oracle/make_golden.py polar` "
-               "rewrites every polar_ref_*.txt.gz (SC-list decoder, encoder, trellis kernel processor).")
+               "rewrites every polar_ref_*.txt.gz (SC-list decoder, encoder, trellis kernel processor, its "
+               "operation counts, the BEC capacity evaluator).")
     ap.add_argument("what", nargs="?", default="kaneko", choices=["kaneko", "polar"])
     {"kaneko": kaneko, "polar": polar}[ap.parse_args().what]()
 

@@ -10,8 +10,11 @@
 // file layout and GetSubchannelCapacity's Horner rule), CArikanKernel::GetSubchannelCapacity
 // (out/external/Kernel.cpp:57-79, ec_BEC), CMatrixBinaryKernel's file reader (Kernel.cpp:93-134:
 // size, matrix, then per-channel sections, ec_BEC = 3 in headers/external/Simulator.h:13-17).
-// The reference's evaluator needs GSL headers and is never built: the Horner rule is restated,
-// parity unpinned. The tables themselves come from csrc/kernel_bec.hip.
+// The Horner rule is restated and pinned to the compiled reference evaluator, and the writer to
+// the reference's reader, by tests/golden/polar_ref_capacity_*.txt.gz (tests/test_polar_design.py):
+// equal bits on every recorded row but C = 0. The design recursion does not use that rule for
+// matrix layers (design_row below): it is accurate only for capacities near 1/2. The tables
+// themselves come from csrc/kernel_bec.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -65,12 +68,54 @@ struct Layer {
     bool arikan = true;
     int l = 2;
     std::vector<double> tab;  // [l][l + 1], matrix layers
+    std::vector<double> cor;  // [l][l + 1]: C(l, w) - tab, the correctable patterns, clamped at 0
 };
+
+// The same capacity as the sum over the CORRECTABLE patterns, sum_w d[w] P^w C^(l-w) with
+// d[w] = C(l, w) - u[w] >= 0: no term is negative, so nothing cancels, and the value keeps its
+// relative accuracy down to underflow, where capacity_row's 1 - E is rounding noise once the
+// capacity falls below 1e-16 and NaN once S^l overflows. The larger of P and C is factored out,
+// so Horner runs in a ratio r <= 1 and the one power taken is of a number >= 1/2: nothing
+// overflows, and nothing underflows before the result does. At C = 0 this is d[l] = 1 - u[l],
+// at C = 1 d[0] = 1. For l <= 56 the d[w] are exact; the relative error is then at most
+// (5 l + 4) 2^-53: r carries 2 roundings and each of the at most l multiplications one more, l
+// additions of non-negative terms, the base of the power one rounding taken l times, pow and
+// the last product.
+double design_row(const double *d, int l, double C) {
+    const double P = 1.0 - C;
+    double E;
+    if (C <= P) {
+        const double r = C / P;
+        E = d[0];
+        for (int w = 1; w <= l; ++w) E = E * r + d[w];
+        E *= std::pow(P, l);
+    } else {
+        const double r = P / C;
+        E = d[l];
+        for (int w = l - 1; w >= 0; --w) E = E * r + d[w];
+        E *= std::pow(C, l);
+    }
+    return E < 1.0 ? E : 1.0;  // E >= 0: every operand is
+}
+
+// C(l, w) - tab per phase; a sampled table's estimate may pass C(l, w) by rounding
+void correctable_table(Layer &L) {
+    const int l = L.l;
+    std::vector<long double> binom(l + 1, 1.0L);
+    for (int w = 1; w <= l; ++w) binom[w] = binom[w - 1] * (long double)(l - w + 1) / (long double)w;
+    L.cor.resize(L.tab.size());
+    for (int i = 0; i < l; ++i)
+        for (int w = 0; w <= l; ++w) {
+            // the file stores a 0 at w = 0 whatever the table holds there; no phase is lost unerased
+            const long double v = binom[w] - (w ? (long double)L.tab[(size_t)i * (l + 1) + w] : 0.0L);
+            L.cor[(size_t)i * (l + 1) + w] = v > 0.0L ? (double)v : 0.0;
+        }
+}
 
 // T_phase(C) of one layer (Kernel.cpp:70-75 for the Arikan kernel)
 double layer_capacity(const Layer &L, int phase, double C) {
     if (L.arikan) return phase == 0 ? C * C : 2 * C - C * C;
-    return capacity_row(&L.tab[(size_t)phase * (L.l + 1)], L.l, C);
+    return design_row(&L.cor[(size_t)phase * (L.l + 1)], L.l, C);
 }
 
 // A matrix kernel file (Kernel.cpp:93-134): the size, the matrix, then channel sections; the
@@ -211,6 +256,7 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
                 if (!invertible(Km, L[j].l)) return dfail(BCHK_EINVAL, "Kernel is singular (%s)", name.c_str() + 1);
                 if (!has)
                     if (int rc = device_table(Km, L[j].l, samples, seed, device, L[j].tab)) return rc;
+                correctable_table(L[j]);
                 seen[name.substr(1)] = j;
             }
             U *= L[j].l;

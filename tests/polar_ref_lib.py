@@ -1,5 +1,6 @@
 """The tests/golden/polar_ref_*.txt.gz fixtures: inputs and RECORDED OUTPUTS of the reference's
-vendored polar library itself (its SC-list decoder, encoder and trellis kernel processor),
+vendored polar library itself (its SC-list decoder, encoder, trellis kernel processor with its
+operation counters, kernel-file reader and BEC capacity evaluator),
 compiled into oracle/_ref/polar_ref by oracle/Makefile and run by `oracle/make_golden.py
 polar`. Data only. Shared by that generator and tests/test_polar_reference.py.
 
@@ -15,6 +16,16 @@ by its nlines lines:
   @trellis_in      per line '<u bits> <y f32 hex ...>'               (kernel processor input)
   @trellis_out     polar_ref's stdout: per line the l kernel-input LLRs (phase p given
                    u_0..u_{p-1}), f32 hex
+  @lu_code c       (no lines) the kernel is the field-ordered 16 x 16 extended-BCH kernel with
+                   its columns mapped by candidate code c of the column search
+  @counts_in       channel LLR rows, f32 hex                         (column-search score input)
+  @counts_out      polar_ref's stdout: per row '<SumCount growth> <CmpCount growth>' over GetLLRs
+                   at every phase in order, zero known inputs (root bchCoder.cpp:641-653)
+  @kernel_file F   kernel file F, its text line by line exactly as bchk_kernel_write_file wrote
+                   it: size, matrix, '3', the BEC table (Kernel.cpp:93-134)
+  @capacity_in     channel capacities, one per line, f64 as hex bits
+  @capacity_out    polar_ref's stdout: per capacity GetSubchannelCapacity(ec_BEC, phase, .) of
+                   every phase, f64 hex bits (CapacityEvaluator.cpp:124-140, NaN and -inf included)
 """
 import glob
 import gzip
@@ -29,14 +40,22 @@ POLAR_REF = os.path.join(REPO, "oracle", "_ref", "polar_ref")
 
 
 def fixture_files(kind):
-    """kind 'code' (decoder + encoder fixtures) or 'trellis'."""
+    """kind 'code' (decoder + encoder fixtures), 'trellis', 'counts' or 'capacity'."""
     all_ = sorted(glob.glob(os.path.join(GOLD, "polar_ref_*.txt.gz")))
-    tr = [p for p in all_ if os.path.basename(p).startswith("polar_ref_trellis_")]
-    return tr if kind == "trellis" else [p for p in all_ if p not in tr]
+    by = {k: [p for p in all_ if os.path.basename(p).startswith(f"polar_ref_{k}_")] for k in ("trellis", "counts", "capacity")}
+    return by[kind] if kind in by else [p for p in all_ if not any(p in v for v in by.values())]
 
 
 def hex_row(a):
     return " ".join(f"{int(x):08x}" for x in np.ascontiguousarray(a, np.float32).view(np.uint32))
+
+
+def hex64(v):
+    return f"{int(np.float64(v).view(np.uint64)):016x}"
+
+
+def f64_row(line):
+    return np.array([int(w, 16) for w in line.split()], np.uint64).view(np.float64)
 
 
 def bits_row(a):
@@ -114,10 +133,35 @@ class Fixture:
             i += 1 + c
         return out
 
+    @property
+    def kernel_file(self):
+        """(name, text) of the fixture's '@kernel_file' section."""
+        for n, a, lines in self.sections:
+            if n == "kernel_file":
+                return a[0], "\n".join(lines) + "\n"
+        raise KeyError("kernel_file")
+
+    @property
+    def counts(self):
+        """(y f32 [rows][l], [(Sum, Cmp)] per row)."""
+        y = np.array([[int(w, 16) for w in r.split()] for r in self.get("counts_in")], np.uint32).view(np.float32)
+        return y, [tuple(int(v) for v in r.split()) for r in self.get("counts_out")]
+
+    @property
+    def lu_code(self):
+        for n, a, _ in self.sections:
+            if n == "lu_code":
+                return int(a[0])
+        return None
+
     def write_kernels(self, d):
         for fname, K in self.kernels.items():
             with open(os.path.join(d, fname), "w") as f:
                 f.write(kernel_text(K))
+        if self.has("kernel_file"):
+            fname, text = self.kernel_file
+            with open(os.path.join(d, fname), "w") as f:
+                f.write(text)
 
     # ---- file form
     def dumps(self):
@@ -153,6 +197,23 @@ def load_fixture(path):
     return fx
 
 
+_modes = {}
+
+
+def ref_lacks(mode, binary=POLAR_REF):
+    """Why a regeneration test of `mode` cannot run, or None. The binary names its modes in its
+    usage line (no arguments: exit 2); one built from a driver older than the mode does not name
+    it, and is as good as absent for that mode."""
+    if not os.path.exists(binary):
+        return "oracle/_ref/polar_ref is not built (the reference tree is absent)"
+    if binary not in _modes:
+        r = subprocess.run([binary], capture_output=True, text=True, stdin=subprocess.DEVNULL)
+        _modes[binary] = r.stderr
+    if f" {mode} " not in _modes[binary]:
+        return f"oracle/_ref/polar_ref was built from a driver without the `{mode}` mode (rebuild: make -C oracle ref)"
+    return None
+
+
 def run_ref(args, stdin_lines, cwd, binary=POLAR_REF):
     r = subprocess.run([binary] + [str(a) for a in args], input="\n".join(stdin_lines) + "\n",
                        capture_output=True, text=True, cwd=cwd)
@@ -177,5 +238,10 @@ def regenerate(fx, workdir, binary=POLAR_REF):
         elif n == "trellis_out":
             (kfile,) = fx.kernels.keys()
             lines = run_ref(["trellis", kfile], fx.get("trellis_in"), workdir, binary)
+        elif n == "counts_out":
+            (kfile,) = fx.kernels.keys()
+            lines = run_ref(["counts", kfile], fx.get("counts_in"), workdir, binary)
+        elif n == "capacity_out":
+            lines = run_ref(["capacity", fx.kernel_file[0]], fx.get("capacity_in"), workdir, binary)
         out.sections.append((n, a, lines))
     return out

@@ -6,8 +6,10 @@ root bchCoder.cpp:356-389 (makeMatrix), :478-496 (swapColumns' field-element ord
 The checker is oracle/kernel_oracle.c, which builds and walks the reference's trellis state
 by state; its LLRs are pinned here to an independent coset enumeration (the min-sum the
 trellis computes), its kernel to the restatement in test_polar_mixed.py. The operation
-counts themselves are parity unpinned: the vendored library cannot be built here and the
-SectionedTrellisKernelProcessor randomSwapColumns names is absent from the reference.
+counts themselves are pinned to the compiled vendored library's SumCount / CmpCount by
+tests/golden/polar_ref_counts_*.txt.gz (tests/test_kernel_search_reference.py: the oracle and
+the GPU, each directly). Still unpinned: the search's acceptance rule and candidate draws --
+the SectionedTrellisKernelProcessor randomSwapColumns names is absent from the reference.
 The GPU (csrc/kernel_search.hip, closed form from the minimum-span structure) must match the
 oracle's counts exactly."""
 import ctypes as C
