@@ -31,7 +31,7 @@ namespace bchk {
 namespace {
 
 using penc::ubit;
-using penc::wave_sync;
+using plist::wsync;
 
 __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGenParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t psm[];
@@ -55,7 +55,7 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
         } else {
             penc::pack_info(p.info_in + w * (uint64_t)K, K, ib, lane);
         }
-        wave_sync();
+        wsync();
         if (p.gen && p.info) {
             uint8_t *out = p.info + w * (uint64_t)K;
             for (int r = lane; r < K; r += 64) out[r] = (uint8_t)((ib[r >> 6] >> (r & 63)) & 1ull);
@@ -102,7 +102,7 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
                 src = dst;
                 dst = tmp;
             }
-            wave_sync();
+            wsync();
             stride = next;
         }
         // ---- the transmitted symbols, and LLR = -2 y / var of y = BPSK + sigma z
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
                 }
             }
         }
-        wave_sync();  // the next word overwrites the buffers
+        wsync();  // the next word overwrites the buffers
     }
 }
 

@@ -1,5 +1,7 @@
-// polar_device.h -- structures shared by the host runtime (polar_host.cpp) and the gfx950
-// SC-list kernel (polar_sclist.hip). Plain C++, no HIP types.
+// polar_device.h -- what the host runtime (polar_host.cpp) shares with the gfx950 polar
+// kernels: the parameter blocks, LDS layouts and save-slot format of the SC-list decoders
+// (polar_sclist.hip, polar_mixed.hip), the simulation front-end (polar_channel.hip) and
+// genie-aided SC (polar_genie.hip). Plain C++, no HIP types.
 #pragma once
 #include <stdint.h>
 
@@ -51,10 +53,18 @@ constexpr int kPolarMaxTrellisKernel = 32;  // the trellis is built for kernels 
 #endif
 constexpr int kMlStack = BCHK_ML_STACK;
 constexpr int kMlEnumBits = 10;
-constexpr uint32_t kMlScratchBytes = 12u * kMlStack + 8u * 64u + 8u * 65u + 8u + 4u * 64u + 4u * 64u;
-// the scratch before the stack (G, U, cost, ay: polar_mixed.hip MlScratch), saved with a
-// suspended search together with the stack's live nodes
-constexpr uint32_t kMlHeadBytes = 8u * 64u + 8u * 65u + 8u + 4u * 64u + 4u * 64u;
+// The scratch's carve-up (polar_mixed.hip MlScratch), each array where the one before ends:
+// G at 0, then
+constexpr uint32_t kMlOffU = 8u * 64u;                    // past G [64] u64
+constexpr uint32_t kMlOffCost = kMlOffU + 8u * 65u + 8u;  // past U [65] u64 and 8 bytes of padding
+constexpr uint32_t kMlOffAy = kMlOffCost + 4u * 64u;      // past cost [64] f32
+// the scratch before the stack (G, U, cost, ay), saved with a suspended search together with
+// the stack's live nodes
+constexpr uint32_t kMlHeadBytes = kMlOffAy + 4u * 64u;    // past ay [64] f32: the stack
+constexpr uint32_t kMlNodeBytes = 12u;                    // sizeof(MlNode)
+constexpr uint32_t kMlScratchBytes = kMlHeadBytes + kMlNodeBytes * kMlStack;
+// u64 arrays on 8 bytes; a save slot takes the head and the live nodes as 32-bit words
+static_assert(kMlOffU % 8 == 0 && kMlHeadBytes % 4 == 0 && kMlNodeBytes % 4 == 0, "search scratch alignment");
 // Matrix layers of size >= the trellis threshold (default 16, BCHK_POLAR_TRELLIS) take their
 // LLRs from CTrellisKernelProcessor's trellis (pull-form Viterbi over predecessor lists);
 // smaller ones enumerate the coset (2^(size - 1 - phase) words per LLR). Per (layer, phase):
@@ -99,7 +109,7 @@ struct PolarMixedParams {
     // per workgroup, not per codeword.
     uint32_t *rstate;
     uint8_t *rsave;         // [grid][rstride]
-    uint32_t rstride;       // bytes of rsave per workgroup (polar_mixed_save_bytes)
+    uint32_t rstride;       // bytes of rsave per workgroup (PolarMixedLayout::save_bytes)
     uint32_t *unfinished;   // codewords left suspended or not started by this launch
     uint32_t *progress;     // search rounds (at least), items and codewords completed by this launch
     uint64_t budget;
@@ -108,12 +118,38 @@ struct PolarMixedParams {
 };
 constexpr uint32_t kMlRoundsDefault = 1u << 20;
 
-// The kernel's LDS offsets (polar_mixed.hip), shared with the host's save-area size.
-struct PolarMixedLayout {
-    int o_S, o_C, o_O, o_ph, o_rows, o_act, o_tm;
+// A suspended codeword's save slot (PolarMixedParams::rsave): the header, six registers per
+// lane, then the LDS of the list state -- channel / S / C / O ([0, o_ph)) at kSaveLdsOff,
+// act / rec ([o_act, o_tm)) at sv_act -- and at sv_ml a suspended search's scratch (its head
+// and live nodes; room for kMlScratchBytes).
+struct PolarSaveHeader {      // (32-bit words 0..14 of the slot)
+    uint32_t phi, layer, item;  // where to resume: phase, layer of its LLR recursion, search item
+    uint32_t k, active, top;    // unfrozen decisions so far, active paths, the path stack's top
+    uint32_t mid;               // suspended inside a search item: the fields below and the scratch
+    uint32_t sp;                // MlResume (polar_mixed.hip): live stack nodes,
+    float best0, best1;
+    uint64_t hd, lrb;
+    uint32_t rounds;
 };
-__host__ __device__ inline PolarMixedLayout polar_mixed_layout(int U, int L, int ssize, int csize, int osize, int nl,
-                                                               int rec_words) {
+struct PolarSaveLane {        // lane q: path q's scalars and slot q of the path stack
+    float R, lv;
+    uint64_t dm;
+    uint32_t rw, slot;
+};
+constexpr uint32_t kSaveHeaderBytes = 64, kSaveLaneBytes = 24;
+constexpr uint32_t kSaveLdsOff = kSaveHeaderBytes + 64u * kSaveLaneBytes;
+static_assert(sizeof(PolarSaveHeader) <= kSaveHeaderBytes && sizeof(PolarSaveLane) == kSaveLaneBytes, "save slot");
+
+// The kernel's LDS offsets (polar_mixed.hip) and size, and the save slot's: channel, per path
+// S / C / offset states, phases, kernel rows, act / rec, the trellis state metrics (two
+// buffers of tstates floats) and, with a search layer (ml), the search scratch.
+struct PolarMixedLayout {
+    int o_S, o_C, o_O, o_ph, o_rows, o_act, o_tm, o_ml;
+    uint32_t bytes;
+    uint32_t sv_act, sv_ml, save_bytes;
+};
+__host__ __device__ inline PolarMixedLayout polar_mixed_layout(int U, int L, int K, int ssize, int csize, int osize,
+                                                               int nl, int tstates, bool ml) {
     PolarMixedLayout o;
     o.o_S = (4 * U + 15) & ~15;
     o.o_C = o.o_S + 4 * ssize * L;
@@ -121,29 +157,13 @@ __host__ __device__ inline PolarMixedLayout polar_mixed_layout(int U, int L, int
     o.o_ph = (o.o_O + osize * L + 15) & ~15;
     o.o_rows = (o.o_ph + 2 * U + 15) & ~15;
     o.o_act = o.o_rows + 8 * kPolarMaxKernel * nl;
-    o.o_tm = (o.o_act + 4 * L + 4 * L * rec_words + 15) & ~15;
+    o.o_tm = (o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15;
+    o.o_ml = (o.o_tm + 8 * tstates + 15) & ~15;
+    o.bytes = ((uint32_t)o.o_ml + (ml ? kMlScratchBytes : 0u) + 15u) & ~15u;
+    o.sv_act = kSaveLdsOff + (uint32_t)o.o_ph;
+    o.sv_ml = o.sv_act + (uint32_t)(o.o_tm - o.o_act);
+    o.save_bytes = (o.sv_ml + kMlScratchBytes + 15u) & ~15u;
     return o;
-}
-// a suspended codeword: header (64 B), six registers per lane (64 x 24 B), then the LDS of
-// the list state: channel / S / C / O ([0, o_ph)) and act / rec ([o_act, o_tm))
-// (+ a suspended search's scratch: kMlScratchBytes)
-__host__ __device__ inline uint32_t polar_mixed_save_bytes(const PolarMixedLayout &o) {
-    return (uint32_t)((64 + 64 * 24 + o.o_ph + (o.o_tm - o.o_act) + kMlScratchBytes + 15) & ~15);
-}
-
-inline uint32_t polar_mixed_lds_bytes(int U, int L, int K, int ssize, int csize, int osize, int nl,
-                                      int tstates, bool ml) {
-    uint32_t b = (4u * (uint32_t)U + 15u) & ~15u;                                     // channel
-    b += 4u * (uint32_t)ssize * (uint32_t)L + (uint32_t)csize * (uint32_t)L;           // S, C
-    b = (b + (uint32_t)osize * (uint32_t)L + 15u) & ~15u;                              // offsets
-    b = (b + 2u * (uint32_t)U + 15u) & ~15u;                                           // phases
-    b += 8u * (uint32_t)kPolarMaxKernel * (uint32_t)nl;                                // rows
-    b += 4u * (uint32_t)L + 4u * (uint32_t)L * (uint32_t)polar_rec_words(K);            // act, rec
-    b = (b + 15u) & ~15u;
-    b += 8u * (uint32_t)tstates;  // trellis state metrics: two buffers of tstates floats
-    b = (b + 15u) & ~15u;
-    if (ml) b += kMlScratchBytes;  // ordered-statistics search scratch
-    return (b + 15u) & ~15u;
 }
 
 // ---- the simulation front-end (polar_channel.hip): encoder, AWGN LLRs, error counters.
@@ -253,17 +273,20 @@ inline int polar_cw_layout(int U, int32_t *off) {
     return w | 1;
 }
 
-// LDS bytes of one wave's state (see polar_sclist.hip): per path S (floats) and the packed
-// partial sums, the active-path list and per path the information bits decided so far. The
-// channel LLRs and the phase table are read from global memory (layer 0 is read at two
-// phases per codeword, the phase word once per phase).
-inline uint32_t polar_lds_bytes(int U, int L, int K) {
-    uint32_t b = 4u * (uint32_t)polar_path_s(U) * (uint32_t)L;             // S
-    b += 4u * (uint32_t)polar_cw_layout(U, nullptr) * (uint32_t)L;          // C (bits)
-    b = (b + 15u) & ~15u;
-    b += 4u * (uint32_t)L;                                                  // active list
-    b += 4u * (uint32_t)L * (uint32_t)polar_rec_words(K);                   // information bits
-    return (b + 15u) & ~15u;
+// LDS of one wave's state (see polar_sclist.hip): per path S (floats, at 0) and the packed
+// partial sums (pathCw = polar_cw_layout's stride), the active-path list and right after it
+// per path the information bits decided so far. The channel LLRs and the phase table are read
+// from global memory (layer 0 is read at two phases per codeword, the phase word once per phase).
+struct PolarListLayout {
+    int o_C, o_act;
+    uint32_t bytes;
+};
+__host__ __device__ inline PolarListLayout polar_list_layout(int U, int L, int K, int pathCw) {
+    PolarListLayout o;
+    o.o_C = 4 * polar_path_s(U) * L;
+    o.o_act = (o.o_C + 4 * pathCw * L + 15) & ~15;
+    o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
+    return o;
 }
 
 }  // namespace bchk

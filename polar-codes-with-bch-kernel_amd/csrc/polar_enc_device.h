@@ -11,21 +11,17 @@
 #include <stdint.h>
 
 #include "polar_device.h"
+#include "polar_list_device.h"
 
 namespace bchk {
 namespace penc {
 
-// LDS written by some lanes of the wave is read by others after this
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using plist::wsync;
 
 __device__ __forceinline__ uint32_t ubit(const uint32_t *u, int pos) { return (u[pos >> 5] >> (pos & 31)) & 1u; }
 
 // information bytes in[0, K) packed: bit r of the word = bit r & 63 of ib[r >> 6]
-// (wave_sync before another lane reads ib)
+// (wsync before another lane reads ib)
 __device__ __forceinline__ void pack_info(const uint8_t *in, int K, uint64_t *ib, int lane) {
     for (int g = 0; g * 64 < K; ++g) {
         const int r = g * 64 + lane;
@@ -46,7 +42,7 @@ __device__ __forceinline__ void build_u(const PolarEncTables &t, const uint64_t 
         const uint64_t m = __ballot(r >= 0 && ((ib[r >> 6] >> (r & 63)) & 1ull));
         if (lane == 0) ua[g] = m;
     }
-    wave_sync();
+    wsync();
     uint32_t *u32 = reinterpret_cast<uint32_t *>(ua);
     for (int d = 0; d < t.ndyn; ++d) {
         const uint32_t a = t.dynoff[d], e = t.dynoff[d + 1] - 1u;  // terms [a, e), the symbol at e
@@ -55,7 +51,7 @@ __device__ __forceinline__ void build_u(const PolarEncTables &t, const uint64_t 
         const uint32_t par = (uint32_t)__popcll(__ballot(v != 0)) & 1u;
         const int sym = t.dynterm[e];
         if (par && lane == 0) u32[sym >> 5] |= 1u << (sym & 31);
-        wave_sync();
+        wsync();
     }
 }
 

@@ -19,6 +19,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <vector>
@@ -75,10 +76,11 @@ struct PBuf {
         cap = bytes;
         return 0;
     }
-    void release() {
+    PBuf() = default;
+    PBuf(const PBuf &) = delete;
+    PBuf &operator=(const PBuf &) = delete;
+    ~PBuf() {
         if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
     }
 };
 
@@ -128,10 +130,10 @@ struct bchk_polar {
 
 namespace {
 
-// bytes of one workgroup's save slot (a suspended codeword, polar_device.h)
-uint32_t polar_save_stride(const bchk_polar *c) {
+// the mixed kernel's LDS and save-slot layout (polar_device.h)
+PolarMixedLayout mixed_lds(const bchk_polar *c) {
     const PolarMixedParams &m = c->mp;
-    return polar_mixed_save_bytes(polar_mixed_layout(c->U, c->L, m.ssize, m.csize, m.osize, m.nl, polar_rec_words(c->K)));
+    return polar_mixed_layout(c->U, c->L, c->K, m.ssize, m.csize, m.osize, m.nl, m.tstates, m.any_ml != 0);
 }
 
 // The specification (MixedKernelEncoder.cpp:7-98): header, kernel names, shortened and
@@ -434,13 +436,11 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     if (list_size < 1 || list_size > kPolarMaxList)
         return pfail(BCHK_EINVAL, "list size %d unsupported (1..%d)", list_size, kPolarMaxList);
     // the specification is checked first, so malformed codes are reported with or without a GPU
-    bchk_polar *c = new bchk_polar();
+    std::unique_ptr<bchk_polar, void (*)(bchk_polar *)> ctx(new bchk_polar(), bchk_polar_destroy);
+    bchk_polar *const c = ctx.get();
     c->L = list_size;
     c->device = device;
-    if (int rc = parse_spec(c, spec, kdir)) {
-        delete c;
-        return rc;
-    }
+    if (int rc = parse_spec(c, spec, kdir)) return rc;
     if (c->mixed) {
         PolarMixedParams &m = c->mp;
         const int nl = c->n;
@@ -467,41 +467,24 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
             const int most = build_trellis(&c->krows[(size_t)j * kPolarMaxKernel], c->ksize[j], c->tent,
                                            &c->tbase[(size_t)j * kPolarMaxKernel],
                                            &c->tlog[(size_t)j * kPolarMaxKernel * (kPolarMaxKernel + 1)]);
-            if (!most) {
-                delete c;
-                return BCHK_EINVAL;  // build_trellis set the message
-            }
+            if (!most) return BCHK_EINVAL;  // build_trellis set the message
             m.tstates = std::max(m.tstates, std::max(64, most));
         }
         if (c->tent.empty()) c->tent.push_back(0u);
-        c->lds = polar_mixed_lds_bytes(c->U, c->L, c->K, m.ssize, m.csize, m.osize, nl, m.tstates, m.any_ml != 0);
+        c->lds = mixed_lds(c).bytes;
     } else {
-        c->lds = polar_lds_bytes(c->U, c->L, c->K);
+        c->lds = polar_list_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     }
-    if (c->lds > 160 * 1024) {
-        const size_t need = c->lds;
-        const int U = c->U;
-        delete c;
-        return pfail(BCHK_EINVAL, "length %d with list %d needs %zu B of LDS (> 160 KiB)", U, list_size, need);
-    }
+    if (c->lds > 160 * 1024)
+        return pfail(BCHK_EINVAL, "length %d with list %d needs %zu B of LDS (> 160 KiB)", c->U, list_size, c->lds);
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        delete c;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return pfail(BCHK_ENODEV, "no HIP device visible (the SC-list decoder has no CPU fallback)");
-    }
-    if (device < 0 || device >= ndev) {
-        delete c;
-        return pfail(BCHK_EINVAL, "device %d out of range", device);
-    }
+    if (device < 0 || device >= ndev) return pfail(BCHK_EINVAL, "device %d out of range", device);
     hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        delete c;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess || strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return pfail(BCHK_ENODEV, "device %d is not gfx950; libbchk is built for gfx950 only", device);
-    }
-    if (hipSetDevice(device) != hipSuccess) {
-        delete c;
-        return pfail(BCHK_EHIP, "hipSetDevice(%d) failed", device);
-    }
+    if (hipSetDevice(device) != hipSuccess) return pfail(BCHK_EHIP, "hipSetDevice(%d) failed", device);
     // device tables, one blob
     auto al = [](size_t v) { return (v + 15) & ~size_t(15); };
     size_t o = 0;
@@ -535,10 +518,8 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     if (!c->dynterm.empty()) memcpy(blob.data() + c->off_dynterm, c->dynterm.data(), 2 * c->dynterm.size());
     if (hipMalloc(&c->d_tab, o) != hipSuccess ||
         hipMemcpy(c->d_tab, blob.data(), o, hipMemcpyHostToDevice) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        bchk_polar_destroy(c);
+        hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return pfail(BCHK_EHIP, "device setup failed");
-    }
     const void *fn = c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
     if (c->lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds);
     int per_cu = 0;
@@ -554,27 +535,12 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         env_double("BCHK_POLAR_BUDGET_MS", &ms, 0.0, DBL_MAX);
         c->budget_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
     }
-    *out = c;
+    *out = ctx.release();
     return 0;
 }
 
 void bchk_polar_destroy(bchk_polar *c) {
     if (!c) return;
-    c->llr.release();
-    c->info.release();
-    c->cw.release();
-    c->metric.release();
-    c->count.release();
-    c->rstate.release();
-    c->rsave.release();
-    c->unfinished.release();
-    c->txinfo.release();
-    c->txcw.release();
-    c->flags.release();
-    c->cnt8.release();
-    c->gdec.release();
-    c->gu.release();
-    c->gsum.release();
     if (c->d_tab) (void)hipFree(c->d_tab);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -589,7 +555,7 @@ int bchk_polar_last_launches(const bchk_polar *c, uint64_t *launches) {
 int bchk_polar_scratch_bytes(const bchk_polar *c, uint64_t *bytes, uint64_t *save_stride) {
     if (!c || !bytes) return pfail(BCHK_EINVAL, "NULL argument");
     *bytes = (uint64_t)c->rstate.cap + c->rsave.cap + c->unfinished.cap;
-    if (save_stride) *save_stride = (c->mixed && c->mp.any_ml) ? polar_save_stride(c) : 0;
+    if (save_stride) *save_stride = (c->mixed && c->mp.any_ml) ? mixed_lds(c).save_bytes : 0;
     return 0;
 }
 
@@ -657,7 +623,7 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         // state saved is the whole list state). The call returns when every codeword is done.
         // A workgroup has at most one suspended codeword (PolarMixedParams), and the grid is
         // the same for every launch of the call: one save slot per workgroup.
-        const uint32_t stride = polar_save_stride(c);
+        const uint32_t stride = mixed_lds(c).save_bytes;
         int rc;
         if ((rc = c->rstate.ensure(B * 4)) || (rc = c->rsave.ensure((size_t)grid * stride)) ||
             (rc = c->unfinished.ensure(8)))

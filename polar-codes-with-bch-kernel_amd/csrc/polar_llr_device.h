@@ -20,15 +20,12 @@
 #include <stdint.h>
 
 #include "polar_device.h"
+#include "polar_list_device.h"
 
 namespace bchk {
 namespace pllr {
 
-__device__ __forceinline__ void wsync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using plist::wsync;
 
 // min over the words of one half of the coset (CTrellisKernelProcessor::GetLLRs, :272-292):
 // words c = XOR of rows phase+1 .. l-1 selected by v, v = first, first + step, ...; metric of

@@ -21,49 +21,14 @@
 #include <stdint.h>
 
 #include "polar_device.h"
+#include "polar_list_device.h"
 #include "polar_llr_device.h"
 
 namespace bchk {
 
 namespace {
 
-using pllr::wsync;
-
-constexpr uint32_t kUninitM = 0xFFFFFFFFu;
-
-__device__ __forceinline__ float rdlf_m(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ uint32_t rdlu_m(uint32_t v, int l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-__device__ __forceinline__ uint64_t rdlu64_m(uint64_t v, int l) {
-    return (uint64_t)rdlu_m((uint32_t)v, l) | ((uint64_t)rdlu_m((uint32_t)(v >> 32), l) << 32);
-}
-
-struct MStack {  // TVMemoryEngine's path-index stack with lazy initialisation (misc.h:212-226)
-    uint32_t slot;
-    int top;
-    __device__ __forceinline__ void reset(int L, int lane) {
-        top = L;
-        if (lane == L) slot = kUninitM;
-    }
-    __device__ __forceinline__ uint32_t pop(int lane) {
-        const uint32_t v = rdlu_m(slot, top);
-        if (v == kUninitM) {
-            const int r = top - 1;
-            top = r;
-            if (r > 0 && lane == r) slot = kUninitM;
-            return (uint32_t)r;
-        }
-        --top;
-        return v;
-    }
-    __device__ __forceinline__ void push(uint32_t x, int lane) {
-        ++top;
-        if (lane == top) slot = x;
-    }
-};
+using namespace plist;
 
 // ---- exact kernel LLRs by an ordered-statistics search (matrix kernels beyond the trellis
 // limit, e.g. the 64 x 64 extended-BCH kernel of root bchCoder.cpp:356-389 makeMatrix).
@@ -82,6 +47,7 @@ struct MlNode {  // the words c ^ G[i] (and below them): flip cost so far lb, ha
     uint32_t clo, chi;
     uint32_t lbib;  // lb's float bits with the low 7 mantissa bits replaced by i << 1 | b
 };                  // (truncating a non-negative float lowers it: still a lower bound)
+static_assert(sizeof(MlNode) == kMlNodeBytes, "the stack's stride in LDS and in a save slot");
 __device__ __forceinline__ MlNode ml_node(uint64_t c, float lb, int i, int b) {
     return MlNode{(uint32_t)c, (uint32_t)(c >> 32), (__float_as_uint(lb) & ~0x7Fu) | ((uint32_t)i << 1) | (uint32_t)b};
 }
@@ -91,6 +57,11 @@ struct MlScratch {
     float *cost;   // [64] flip cost of each basis row (|y| at its pivot)
     float *ay;     // [64] |y| by position
     MlNode *stk;   // [kMlStack]
+    // carved out of kMlScratchBytes of LDS at mls (polar_device.h)
+    __device__ explicit MlScratch(uint8_t *mls)
+        : G(reinterpret_cast<uint64_t *>(mls)), U(reinterpret_cast<uint64_t *>(mls + kMlOffU)),
+          cost(reinterpret_cast<float *>(mls + kMlOffCost)), ay(reinterpret_cast<float *>(mls + kMlOffAy)),
+          stk(reinterpret_cast<MlNode *>(mls + kMlHeadBytes)) {}
 };
 // a subtree is dropped when lb * kMlShrink > best: a float sum of at most 64 non-negative terms
 // is within 64 u (u = 2^-24) of the exact sum, for lb and for every metric, so the margin
@@ -330,6 +301,37 @@ __device__ float ml_llr(const uint64_t *kr, int l, int loc, const float *src, co
     return best1 - best0;  // (:292)
 }
 
+// A wave-uniform value that came through a vector load, into scalar registers.
+// (readfirstlane returns int: through uint32_t, or a low word sign-extends)
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float uni(float v) { return __uint_as_float(uni(__float_as_uint(v))); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) {
+    return (uint64_t)uni((uint32_t)v) | ((uint64_t)uni((uint32_t)(v >> 32)) << 32);
+}
+
+// ---- a save slot's LDS regions (polar_device.h PolarSaveHeader), one routine for both
+// directions so that suspend and resume cannot drift: kSave copies LDS to the slot, else the
+// slot to LDS, as 32-bit words. The caller issues wsync() before other lanes read restored LDS.
+template <bool kSave>
+__device__ __forceinline__ void slot_copy(uint8_t *slot, uint8_t *lds, int bytes, int lane) {
+    for (int i = 4 * lane; i < bytes; i += 256) {
+        uint32_t *g = reinterpret_cast<uint32_t *>(slot + i), *l = reinterpret_cast<uint32_t *>(lds + i);
+        if (kSave) *g = *l;
+        else *l = *g;
+    }
+}
+// the list state: channel / S / C / O, and act / rec
+template <bool kSave>
+__device__ __forceinline__ void slot_list_state(uint8_t *sv, uint8_t *smem, const PolarMixedLayout &lo, int lane) {
+    slot_copy<kSave>(sv + kSaveLdsOff, smem, lo.o_ph, lane);
+    slot_copy<kSave>(sv + lo.sv_act, smem + lo.o_act, lo.o_tm - lo.o_act, lane);
+}
+// a suspended search's scratch at mls: G, U, cost, ay and the stack's first sp nodes
+template <bool kSave>
+__device__ __forceinline__ void slot_search(uint8_t *sv, uint8_t *mls, const PolarMixedLayout &lo, int sp, int lane) {
+    slot_copy<kSave>(sv + lo.sv_ml, mls, (int)kMlHeadBytes + (int)kMlNodeBytes * sp, lane);
+}
+
 }  // namespace
 
 __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
@@ -337,23 +339,19 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     const int lane = (int)threadIdx.x;
     const int U = p.U, nl = p.nl, L = p.L, K = p.K;
     const int RW = polar_rec_words(K);
-    // LDS: polar_mixed_lds_bytes (polar_device.h)
-    const PolarMixedLayout lo = polar_mixed_layout(U, L, p.ssize, p.csize, p.osize, nl, RW);
-    const int o_S = lo.o_S, o_C = lo.o_C, o_O = lo.o_O, o_ph = lo.o_ph, o_rows = lo.o_rows, o_act = lo.o_act,
-              o_tm = lo.o_tm;
+    // LDS: polar_mixed_layout (polar_device.h)
+    const PolarMixedLayout lo = polar_mixed_layout(U, L, K, p.ssize, p.csize, p.osize, nl, p.tstates, p.any_ml != 0);
     float *chan = reinterpret_cast<float *>(smem);
-    float *S = reinterpret_cast<float *>(smem + o_S);
-    uint8_t *C = smem + o_C;
-    uint8_t *O = smem + o_O;
-    uint16_t *ph = reinterpret_cast<uint16_t *>(smem + o_ph);
-    uint64_t *rows = reinterpret_cast<uint64_t *>(smem + o_rows);  // [layer][row] bitmasks
-    uint32_t *act = reinterpret_cast<uint32_t *>(smem + o_act);
+    float *S = reinterpret_cast<float *>(smem + lo.o_S);
+    uint8_t *C = smem + lo.o_C;
+    uint8_t *O = smem + lo.o_O;
+    uint16_t *ph = reinterpret_cast<uint16_t *>(smem + lo.o_ph);
+    uint64_t *rows = reinterpret_cast<uint64_t *>(smem + lo.o_rows);  // [layer][row] bitmasks
+    uint32_t *act = reinterpret_cast<uint32_t *>(smem + lo.o_act);
     uint32_t *rec = act + L;
-    float *tmet = reinterpret_cast<float *>(smem + o_tm);  // trellis state metrics, 2 x tstates
-    uint8_t *mls = smem + ((o_tm + 8 * p.tstates + 15) & ~15);  // ordered-statistics search scratch
-    MlScratch ms{reinterpret_cast<uint64_t *>(mls), reinterpret_cast<uint64_t *>(mls + 512),
-                 reinterpret_cast<float *>(mls + 1040), reinterpret_cast<float *>(mls + 1296),
-                 reinterpret_cast<MlNode *>(mls + 1552)};
+    float *tmet = reinterpret_cast<float *>(smem + lo.o_tm);  // trellis state metrics, 2 x tstates
+    uint8_t *mls = smem + lo.o_ml;  // ordered-statistics search scratch
+    const MlScratch ms(mls);
     const bool mine = lane < L;
     for (int i = lane; i < U; i += 64) ph[i] = p.phase[i];
     for (int i = lane; i < kPolarMaxKernel * nl; i += 64) rows[i] = p.krows[i];
@@ -362,14 +360,9 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     auto Oof = [&](int q, int j) -> uint8_t * { return O + (size_t)q * p.osize + p.ooff[j]; };
     auto pathof = [&](int k) -> int { return (int)act[k]; };  // the k-th active path
     const pllr::Trellis tr{p.tent, p.tbase, p.tlog, tmet, p.tstates};
-    auto list_act = [&](uint32_t active) {
-        if (mine && ((active >> lane) & 1u)) act[__builtin_popcount(active & ((1u << lane) - 1u))] = (uint32_t)lane;
-        wsync();
-        return __builtin_popcount(active);
-    };
     const int lastsz = p.ksize[nl - 1];
     const int lastc = p.coff[nl];
-    MStack st;
+    PathStack st;
     st.slot = 0;
     wsync();
     // time-budgeted launches (PolarMixedParams::budget): this launch's start on the 100 MHz clock
@@ -394,29 +387,28 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
         }
         worked = true;
         uint32_t active;
-        float R = 0.0f, lv = 0.0f;
-        uint64_t dm = 0;
-        uint32_t rw = 0;
+        PathRegs pr{0.0f, 0.0f, 0ull, 0u};
         int k = 0, phi0 = 0, rj = -1, rit = 0;  // rj >= 0: resume in layer rj at item rit
+        MlResume mr{0, 0.0f, 0.0f, 0ull, 0ull, 0u};
+        bool rmid = false;  // resuming inside a search item (its scratch saved too)
         if (cst == 1u) {
             // resume a suspended codeword: header, registers, the list state's LDS
-            const uint32_t *hd = reinterpret_cast<const uint32_t *>(sv);
-            phi0 = (int)__builtin_amdgcn_readfirstlane(hd[0]);
-            rj = (int)__builtin_amdgcn_readfirstlane(hd[1]);
-            rit = (int)__builtin_amdgcn_readfirstlane(hd[2]);
-            k = (int)__builtin_amdgcn_readfirstlane(hd[3]);
-            active = __builtin_amdgcn_readfirstlane(hd[4]);
-            st.top = (int)__builtin_amdgcn_readfirstlane(hd[5]);
-            const uint32_t *rg = hd + 16 + 6 * lane;
-            R = __uint_as_float(rg[0]);
-            lv = __uint_as_float(rg[1]);
-            dm = (uint64_t)rg[2] | ((uint64_t)rg[3] << 32);
-            rw = rg[4];
-            st.slot = rg[5];
-            const uint8_t *ls = sv + 64 + 64 * 24;
-            for (int i = 4 * lane; i < o_ph; i += 256) *reinterpret_cast<uint32_t *>(smem + i) = *reinterpret_cast<const uint32_t *>(ls + i);
-            for (int i = 4 * lane; i < o_tm - o_act; i += 256)
-                *reinterpret_cast<uint32_t *>(smem + o_act + i) = *reinterpret_cast<const uint32_t *>(ls + o_ph + i);
+            const PolarSaveHeader h = *reinterpret_cast<const PolarSaveHeader *>(sv);
+            phi0 = (int)uni(h.phi);
+            rj = (int)uni(h.layer);
+            rit = (int)uni(h.item);
+            k = (int)uni(h.k);
+            active = uni(h.active);
+            st.top = (int)uni(h.top);
+            const PolarSaveLane g = reinterpret_cast<const PolarSaveLane *>(sv + kSaveHeaderBytes)[lane];
+            pr = PathRegs{g.R, g.lv, g.dm, g.rw};
+            st.slot = g.slot;
+            slot_list_state<false>(sv, smem, lo, lane);
+            rmid = uni(h.mid) != 0u;
+            if (rmid) {
+                mr = MlResume{(int)uni(h.sp), uni(h.best0), uni(h.best1), uni(h.hd), uni(h.lrb), uni(h.rounds)};
+                slot_search<false>(sv, mls, lo, mr.sp, lane);
+            }
         } else {
             const float *y = p.llr + (size_t)cw * p.N;  // LoadLLRs (MixedKernelEncoder.cpp:181-207)
             for (int i = lane; i < U; i += 64) {
@@ -428,67 +420,19 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             active = 1u << pid;
         }
         wsync();
-        int nact = list_act(active);
+        int nact = list_active(active, act, lane, L);
         bool progressed = false, yielded = false;
         // suspend between two search items (the list state is complete there: every layer
-        // before rj done, layer rj's offset state applied, items before it done)
-        MlResume mr{0, 0.0f, 0.0f, 0ull, 0ull, 0u};
-        bool rmid = false;  // resuming inside a search item (its scratch saved too)
-        if (cst == 1u) {
-            const uint32_t *hd = reinterpret_cast<const uint32_t *>(sv);
-            rmid = __builtin_amdgcn_readfirstlane(hd[6]) != 0u;
-            if (rmid) {
-                mr.sp = (int)__builtin_amdgcn_readfirstlane(hd[7]);
-                mr.best0 = __uint_as_float(__builtin_amdgcn_readfirstlane(hd[8]));
-                mr.best1 = __uint_as_float(__builtin_amdgcn_readfirstlane(hd[9]));
-                // (readfirstlane returns int: through uint32_t, or the low word sign-extends)
-                mr.hd = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[10]) |
-                        ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[11]) << 32);
-                mr.lrb = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[12]) |
-                         ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane(hd[13]) << 32);
-                mr.rounds = (uint32_t)__builtin_amdgcn_readfirstlane(hd[14]);
-                const uint8_t *ml = sv + 64 + 64 * 24 + o_ph + (o_tm - o_act);
-                const int mb = (int)kMlHeadBytes + 12 * mr.sp;  // G, U, cost, ay, stack[0, sp)
-                for (int i = 4 * lane; i < mb; i += 256) *reinterpret_cast<uint32_t *>(mls + i) = *reinterpret_cast<const uint32_t *>(ml + i);
-                wsync();
-            }
-        }
-        // mid: inside a search item, whose scratch and MlResume go along
+        // before rj done, layer rj's offset state applied, items before it done), or (mid)
+        // inside a search item, whose scratch and MlResume go along
         auto suspend = [&](int phi, int j, int it, bool mid) {
-            uint32_t *hd = reinterpret_cast<uint32_t *>(sv);
-            if (lane == 0) {
-                hd[0] = (uint32_t)phi;
-                hd[1] = (uint32_t)j;
-                hd[2] = (uint32_t)it;
-                hd[3] = (uint32_t)k;
-                hd[4] = active;
-                hd[5] = (uint32_t)st.top;
-                hd[6] = mid ? 1u : 0u;
-                hd[7] = (uint32_t)mr.sp;
-                hd[8] = __float_as_uint(mr.best0);
-                hd[9] = __float_as_uint(mr.best1);
-                hd[10] = (uint32_t)mr.hd;
-                hd[11] = (uint32_t)(mr.hd >> 32);
-                hd[12] = (uint32_t)mr.lrb;
-                hd[13] = (uint32_t)(mr.lrb >> 32);
-                hd[14] = mr.rounds;
-            }
-            if (mid) {
-                uint8_t *ml = sv + 64 + 64 * 24 + o_ph + (o_tm - o_act);
-                const int mb = (int)kMlHeadBytes + 12 * mr.sp;
-                for (int i = 4 * lane; i < mb; i += 256) *reinterpret_cast<uint32_t *>(ml + i) = *reinterpret_cast<const uint32_t *>(mls + i);
-            }
-            uint32_t *rg = hd + 16 + 6 * lane;
-            rg[0] = __float_as_uint(R);
-            rg[1] = __float_as_uint(lv);
-            rg[2] = (uint32_t)dm;
-            rg[3] = (uint32_t)(dm >> 32);
-            rg[4] = rw;
-            rg[5] = st.slot;
-            uint8_t *ls = sv + 64 + 64 * 24;
-            for (int i = 4 * lane; i < o_ph; i += 256) *reinterpret_cast<uint32_t *>(ls + i) = *reinterpret_cast<const uint32_t *>(smem + i);
-            for (int i = 4 * lane; i < o_tm - o_act; i += 256)
-                *reinterpret_cast<uint32_t *>(ls + o_ph + i) = *reinterpret_cast<const uint32_t *>(smem + o_act + i);
+            if (lane == 0)
+                *reinterpret_cast<PolarSaveHeader *>(sv) =
+                    PolarSaveHeader{(uint32_t)phi, (uint32_t)j, (uint32_t)it, (uint32_t)k, active, (uint32_t)st.top,
+                                    mid ? 1u : 0u, (uint32_t)mr.sp, mr.best0, mr.best1, mr.hd, mr.lrb, mr.rounds};
+            if (mid) slot_search<true>(sv, mls, lo, mr.sp, lane);
+            reinterpret_cast<PolarSaveLane *>(sv + kSaveHeaderBytes)[lane] = PolarSaveLane{pr.R, pr.lv, pr.dm, pr.rw, st.slot};
+            slot_list_state<true>(sv, smem, lo, lane);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             if (lane == 0) {
                 p.rstate[cw] = 1u;
@@ -559,54 +503,23 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             }
             if (yielded) break;
             const bool on = mine && ((active >> lane) & 1u);
-            if (on) lv = Sof(lane, nl)[0];
+            if (on) pr.lv = Sof(lane, nl)[0];
             const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
             if (e & kPhaseFrozen) {
-                // ---- ContinuePathsFrozen (MixedKernelListDecoder.cpp:61-98)
-                const int db = (int)((e >> 1) & 127u) - 1;
-                if (on) {
-                    dec = db >= 0 ? (uint32_t)((dm >> db) & 1ull) : 0u;
-                    if ((dec != 0) ^ (lv < 0.0f)) R -= fabsf(lv);
-                }
+                dec = frozen_step(e, on, pr);
             } else {
-                // ---- ContinuePathsUnfrozen (:100-185): candidate 2q + b in lane 2q + b
-                const int q = lane >> 1, b = lane & 1;
-                const float vq = __shfl(lv, q & 31), Rq = __shfl(R, q & 31);
-                const bool valid = q < L && ((active >> q) & 1u);
-                float sc = 0.0f;
-                if (valid) sc = (b == (vq < 0.0f ? 1 : 0)) ? Rq : Rq - fabsf(vq);
-                int rank = 0;  // std::greater<pair<float, unsigned>> (:125)
-                for (uint64_t mm = __ballot(valid); mm; mm &= mm - 1) {
-                    const int o = (int)__builtin_ctzll(mm);
-                    const float so = rdlf_m(sc, o);
-                    rank += (sc < so || (!(so < sc) && lane < o)) ? 1 : 0;
-                }
-                const int J = 2 * nact, keep = J < L ? J : L;
-                const uint64_t sel = __ballot(valid && rank < keep);
-                const uint32_t cont = mine ? (uint32_t)((sel >> (2 * lane)) & 3ull) : 0u;
-                const uint32_t cont_any = (uint32_t)__ballot(cont != 0);
-                const uint32_t clones = (uint32_t)__ballot(cont == 3u);
-                for (uint32_t kill = active & ~cont_any; kill; kill &= kill - 1) st.push((uint32_t)__builtin_ctz(kill), lane);
-                active &= cont_any;
-                dec = cont == 2u ? 1u : (cont == 3u ? (lv < 0.0f ? 1u : 0u) : 0u);
-                for (uint32_t cl = clones; cl; cl &= cl - 1) {
+                const Continuations ct = unfrozen_select(pr, active, nact, st, lane, L);
+                dec = own_decision(ct.cont, pr.lv);
+                // kills done; then the clones, in path order
+                for (uint32_t cl = ct.clones; cl; cl &= cl - 1) {
                     const int l = __builtin_ctz(cl);
                     const int l1 = (int)st.pop(lane);  // ClonePath: the whole path state
                     for (int i = lane; i < p.ssize; i += 64) S[(size_t)l1 * p.ssize + i] = S[(size_t)l * p.ssize + i];
                     for (int i = lane; i < p.csize; i += 64) C[(size_t)l1 * p.csize + i] = C[(size_t)l * p.csize + i];
                     for (int i = lane; i < p.osize; i += 64) O[(size_t)l1 * p.osize + i] = O[(size_t)l * p.osize + i];
                     for (int i = lane; i < (k >> 5); i += 64) rec[l1 * RW + i] = rec[l * RW + i];
-                    const float Rl = rdlf_m(R, l), vl = rdlf_m(lv, l);
-                    const uint64_t dml = rdlu64_m(dm, l);
-                    const uint32_t rwl = rdlu_m(rw, l), decl = rdlu_m(dec, l);
-                    if (lane == l1) {
-                        R = Rl - fabsf(vl);
-                        dm = dml;
-                        rw = rwl;
-                        dec = decl ^ 1u;
-                        lv = vl;
-                    }
+                    clone_regs(pr, dec, l, l1, lane);
                     active |= 1u << l1;
                 }
                 wsync();
@@ -614,16 +527,11 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             const bool now = mine && ((active >> lane) & 1u);
             if (now) {
                 C[(size_t)lane * p.csize + lastc + (phi % lastsz)] = (uint8_t)dec;
-                if (dec) dm ^= corr;
+                apply_correction(now, dec, corr, pr);
             }
             if (!(e & kPhaseFrozen)) {
-                if (now) rw |= dec << (k & 31);
-                ++k;
-                if ((k & 31) == 0) {
-                    if (now) rec[lane * RW + (k >> 5) - 1] = rw;
-                    rw = 0;
-                }
-                nact = list_act(active);
+                record_decision(now, dec, pr, k, rec, RW, lane);
+                nact = list_active(active, act, lane, L);
             } else {
                 wsync();
             }
@@ -635,16 +543,10 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             wsync();
             continue;
         }
-        if ((k & 31) && mine && ((active >> lane) & 1u)) rec[lane * RW + (k >> 5)] = rw;
-        wsync();
-        // ---- final order (:249-267): active paths by (R, index), descending
-        int rk = 0;
         const bool me = mine && ((active >> lane) & 1u);
-        for (uint64_t mm = __ballot(me); mm; mm &= mm - 1) {
-            const int o = (int)__builtin_ctzll(mm);
-            const float ro = rdlf_m(R, o);
-            rk += (R < ro || (!(ro < R) && lane < o)) ? 1 : 0;
-        }
+        flush_record(pr, k, me, rec, RW, lane);
+        // ---- final order (:249-267): active paths by (R, index), descending
+        const int rk = rank_greater(pr.R, me, lane);
         for (int r = 0; r < nact; ++r) {
             const int q = (int)__builtin_ctzll(__ballot(me && rk == r));
             const uint8_t *cq = C + (size_t)q * p.csize;  // C_0: the unshortened codeword
@@ -653,7 +555,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             for (int kk = lane; kk < K; kk += 64) p.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
             if (p.cw)
                 for (int i = lane; i < p.N; i += 64) p.cw[row * p.N + i] = cq[p.cwpos[i]];
-            if (lane == 0) p.metric[row] = rdlf_m(R, q);
+            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
         }
         if (lane == 0) p.count[cw] = nact;
         if (budgeted && lane == 0) {

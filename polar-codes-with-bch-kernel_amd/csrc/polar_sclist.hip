@@ -28,18 +28,13 @@
 #include <stdint.h>
 
 #include "polar_device.h"
+#include "polar_list_device.h"
 
 namespace bchk {
 
 namespace {
 
-constexpr uint32_t kUninit = 0xFFFFFFFFu;
-
-__device__ __forceinline__ void wave_sync_p() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using namespace plist;
 
 // offset of S_λ (λ >= 1) inside one path's LLR array
 __device__ __forceinline__ int s_off(int U, int lam) { return U - (U >> (lam - 1)); }
@@ -51,49 +46,6 @@ __device__ __forceinline__ float f_minsum(float a, float b) {
     return __uint_as_float(__float_as_uint(m) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
 }
 
-__device__ __forceinline__ float rdl_f(float v, int l) {
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l));
-}
-__device__ __forceinline__ uint32_t rdl_u(uint32_t v, int l) {
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-__device__ __forceinline__ uint64_t rdl_u64(uint64_t v, int l) {
-    return (uint64_t)rdl_u((uint32_t)v, l) | ((uint64_t)rdl_u((uint32_t)(v >> 32), l) << 32);
-}
-
-// The path-index stack of TVMemoryEngine (headers/external/misc.h:212-226) with its lazy
-// initialisation: slot i lives in lane i's `slot`, `top` is wave-uniform.
-struct PathStack {
-    uint32_t slot;
-    int top;
-    __device__ __forceinline__ void reset(int L, int lane) {
-        top = L;
-        if (lane == L) slot = kUninit;
-    }
-    __device__ __forceinline__ uint32_t pop(int lane) {
-        const uint32_t v = rdl_u(slot, top);
-        if (v == kUninit) {  // never pushed: hand out top - 1
-            const int r = top - 1;
-            top = r;
-            if (r > 0 && lane == r) slot = kUninit;
-            return (uint32_t)r;
-        }
-        --top;
-        return v;
-    }
-    __device__ __forceinline__ void push(uint32_t x, int lane) {
-        ++top;
-        if (lane == top) slot = x;
-    }
-};
-
-// act[k] = index of the k-th active path; returns their number
-__device__ __forceinline__ int list_active(uint32_t active, uint32_t *act, int lane, int L) {
-    if (lane < L && ((active >> lane) & 1u)) act[__builtin_popcount(active & ((1u << lane) - 1u))] = (uint32_t)lane;
-    wave_sync_p();
-    return __builtin_popcount(active);
-}
-
 }  // namespace
 
 __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
@@ -101,14 +53,13 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
     const int lane = (int)threadIdx.x;
     const int U = p.U, n = p.n, L = p.L, K = p.K;
     const int pathS = polar_path_s(U), pathC = p.pathCw, RW = polar_rec_words(K);
-    // LDS layout: polar_lds_bytes (polar_device.h)
+    // LDS layout: polar_list_layout (polar_device.h)
     // (byte offsets from smem, never through integer casts of the pointers, which would
     // lose the LDS address space and turn every access into a FLAT one)
-    const int o_C = 4 * pathS * L;
-    const int o_act = (o_C + 4 * pathC * L + 15) & ~15;
+    const PolarListLayout lo = polar_list_layout(U, L, K, pathC);
     float *S = reinterpret_cast<float *>(smem);
-    uint32_t *C = reinterpret_cast<uint32_t *>(smem + o_C);  // packed bits, words per path
-    uint32_t *act = reinterpret_cast<uint32_t *>(smem + o_act);
+    uint32_t *C = reinterpret_cast<uint32_t *>(smem + lo.o_C);  // packed bits, words per path
+    uint32_t *act = reinterpret_cast<uint32_t *>(smem + lo.o_act);
     uint32_t *rec = act + L;
     const int lastc = p.cwoff[n];  // C_n: the two inputs of the last Arikan block (one word)
     const bool mine = lane < L;
@@ -130,11 +81,9 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
         st.reset(L, lane);
         const uint32_t pid = st.pop(lane);
         uint32_t active = 1u << pid;
-        float R = 0.0f, lv = 0.0f;
-        uint64_t dm = 0;
-        uint32_t rw = 0;
+        PathRegs pr{0.0f, 0.0f, 0ull, 0u};
         int k = 0;  // unfrozen decisions so far
-        wave_sync_p();
+        wsync();
         int nact = list_active(active, act, lane, L);
 
         for (int phi = 0; phi < U; ++phi) {
@@ -171,47 +120,20 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
                     }
                     dst[s] = r;
                 }
-                wave_sync_p();
+                wsync();
             }
             const bool on = mine && ((active >> lane) & 1u);
-            if (on) lv = S[(size_t)lane * pathS + U - 2];
+            if (on) pr.lv = S[(size_t)lane * pathS + U - 2];
             const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
 
             if (e & kPhaseFrozen) {
-                // ---- ContinuePathsFrozen (MixedKernelListDecoder.cpp:61-98)
-                const int db = (int)((e >> 1) & 127u) - 1;
-                if (on) {
-                    dec = db >= 0 ? (uint32_t)((dm >> db) & 1ull) : 0u;
-                    if ((dec != 0) ^ (lv < 0.0f)) R -= fabsf(lv);
-                }
+                dec = frozen_step(e, on, pr);
             } else {
-                // ---- ContinuePathsUnfrozen (:100-185). Candidate 2q + b (bit b of path q)
-                // sits in lane 2q + b; its score is R (b = hard decision) or R - |llr|.
-                const int q = lane >> 1, b = lane & 1;
-                const float vq = __shfl(lv, q & 31), Rq = __shfl(R, q & 31);
-                const bool valid = q < L && ((active >> q) & 1u);
-                float sc = 0.0f;
-                if (valid) sc = (b == (vq < 0.0f ? 1 : 0)) ? Rq : Rq - fabsf(vq);
-                // rank under std::greater<pair<float, unsigned>> (:125): score, then index
-                int rank = 0;
-                for (uint64_t mm = __ballot(valid); mm; mm &= mm - 1) {
-                    const int o = (int)__builtin_ctzll(mm);
-                    const float so = rdl_f(sc, o);
-                    rank += (sc < so || (!(so < sc) && lane < o)) ? 1 : 0;
-                }
-                const int J = 2 * nact, keep = J < L ? J : L;
-                const uint64_t sel = __ballot(valid && rank < keep);
-                const uint32_t cont = mine ? (uint32_t)((sel >> (2 * lane)) & 3ull) : 0u;
-                const uint32_t cont_any = (uint32_t)__ballot(cont != 0);
-                const uint32_t clones = (uint32_t)__ballot(cont == 3u);
-                // KillPath, in path order (:129-136)
-                for (uint32_t kill = active & ~cont_any; kill; kill &= kill - 1) st.push((uint32_t)__builtin_ctz(kill), lane);
-                active &= cont_any;
-                // continuations (:138-178): 1 -> bit 0, 2 -> bit 1, 3 -> the hard decision
-                // here and its complement in a clone; the score changes only in the clone
-                dec = cont == 2u ? 1u : (cont == 3u ? (lv < 0.0f ? 1u : 0u) : 0u);
-                for (uint32_t cl = clones; cl; cl &= cl - 1) {
+                const Continuations ct = unfrozen_select(pr, active, nact, st, lane, L);
+                dec = own_decision(ct.cont, pr.lv);
+                // kills done; then the clones, in path order
+                for (uint32_t cl = ct.clones; cl; cl &= cl - 1) {
                     const int l = __builtin_ctz(cl);
                     const int l1 = (int)st.pop(lane);  // ClonePath: copy the live state of l
                     {
@@ -240,37 +162,23 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
                             if (i < nr) rec[l1 * RW + i] = vr;
                         }
                     }
-                    const float Rl = rdl_f(R, l), vl = rdl_f(lv, l);
-                    const uint64_t dml = rdl_u64(dm, l);
-                    const uint32_t rwl = rdl_u(rw, l), decl = rdl_u(dec, l);
-                    if (lane == l1) {
-                        R = Rl - fabsf(vl);
-                        dm = dml;
-                        rw = rwl;
-                        dec = decl ^ 1u;
-                        lv = vl;
-                    }
+                    clone_regs(pr, dec, l, l1, lane);
                     active |= 1u << l1;
                 }
-                wave_sync_p();
+                wsync();
             }
             const bool now = mine && ((active >> lane) & 1u);
             if (now) {  // the path's own word: no other lane writes it
                 uint32_t &w = C[(size_t)lane * pathC + lastc];
                 const uint32_t bit = 1u << (phi & 1);
                 w = dec ? (w | bit) : (w & ~bit);
-                if (dec) dm ^= corr;
+                apply_correction(now, dec, corr, pr);
             }
             if (!(e & kPhaseFrozen)) {
-                if (now) rw |= dec << (k & 31);
-                ++k;
-                if ((k & 31) == 0) {
-                    if (now) rec[lane * RW + (k >> 5) - 1] = rw;
-                    rw = 0;
-                }
+                record_decision(now, dec, pr, k, rec, RW, lane);
                 nact = list_active(active, act, lane, L);
             } else {
-                wave_sync_p();
+                wsync();
             }
 
             // ---- IterativelyUpdateC (KernelListEngine.cpp:266-315): the blocks this phase
@@ -305,24 +213,18 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
                             w = (w & ~m2) | (r << sh);
                         }
                     }
-                    wave_sync_p();
+                    wsync();
                     ++lgs;
                     ph2 = psi;
                     --lam;
                 }
             }
         }
-        if ((k & 31) && mine && ((active >> lane) & 1u)) rec[lane * RW + (k >> 5)] = rw;
-        wave_sync_p();
+        const bool me = mine && ((active >> lane) & 1u);
+        flush_record(pr, k, me, rec, RW, lane);
 
         // ---- final order (:249-267): active paths by (R, index), descending
-        int rk = 0;
-        const bool me = mine && ((active >> lane) & 1u);
-        for (uint64_t mm = __ballot(me); mm; mm &= mm - 1) {
-            const int o = (int)__builtin_ctzll(mm);
-            const float ro = rdl_f(R, o);
-            rk += (R < ro || (!(ro < R) && lane < o)) ? 1 : 0;
-        }
+        const int rk = rank_greater(pr.R, me, lane);
         for (int r = 0; r < nact; ++r) {
             const int q = (int)__builtin_ctzll(__ballot(me && rk == r));
             const uint32_t *cq = C + (size_t)q * pathC;  // C_0: the unshortened codeword (bits)
@@ -353,10 +255,10 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
                     }
                 }
             }
-            if (lane == 0) p.metric[row] = rdl_f(R, q);
+            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
         }
         if (lane == 0) p.count[cw] = nact;
-        wave_sync_p();
+        wsync();
     }
 }
 
