@@ -272,6 +272,15 @@ int bchk_syndrome_table_query(int m, int t, const uint32_t *synd, size_t N, uint
 /* Size of that table: distinct keys, bytes, longest probe sequence (buckets). */
 int bchk_syndrome_table_info(int m, int t, uint64_t *keys, uint64_t *bytes, uint32_t *max_probe);
 
+/* Which kernels a context for (m, t) would launch, from the dispatch functions bchk_create
+ * itself calls (no device needed): out[0] = TMAX of the instantiated kernel set, out[1] = a
+ * fast kernel (n <= 63) or first-pattern kernel (m >= 7) precedes the search kernel,
+ * out[2] = the lane pre-pass of the first-pattern kernel, out[3] = the first-pattern
+ * kernel's selection variant (calls without a stats record), out[4] = the search kernels
+ * decode through the syndrome table, out[5] = the analytic tail kernel; out[6], out[7] = 0.
+ * BCHK_EINVAL for every (m, t) bchk_create refuses. */
+int bchk_kernel_info(int m, int t, int32_t out[8]);
+
 /* ---- SC-list decoding of polar codes (the reference's vendored library, which its own
  * CMake target does not build: headers/external/MixedKernelListDecoder.h:10-42). Pinned to
  * that library compiled as it stands, for kernels below 64: decode, encode and the kernel

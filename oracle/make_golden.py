@@ -15,7 +15,8 @@ the reference's vendored polar library. The polar_ref_*.txt.gz format is describ
 tests/polar_ref_lib.py.
 
 Fixture formats (gzip text, one record per line):
-  vectors_*.txt.gz   '# code n k t m gsize G seed S snr X count C' header, then per word
+  vectors_*.txt.gz, vecj15_*.txt.gz (the J = 15 build)
+                     '# code n k t m gsize G seed S snr X count C' header, then per word
                      'W <tx bits> <y_0..y_{n-1} as %a> <res bits | -> <l0 %a> <decodes>
                       <comparisons> <sums> <accepted>'  (src/KanekoKernelProcessor.cpp:335)
   infile_m6t6.txt    the in/infile.txt known answer, same 'W' line (counters absolute)
@@ -40,9 +41,42 @@ VECTORS = [
     (5, 3, 1, 256, 1.0), (5, 3, 11, 256, 4.0),
     (6, 6, 1, 128, 4.0), (6, 6, 13, 192, 4.5), (6, 6, 17, 256, 5.0), (6, 6, 19, 256, 6.0),
     (8, 15, 1, 48, 6.0), (8, 15, 23, 48, 7.0),
+    # the lowest and the top t of the small (m, TMAX) kernel sets (select_kernels), and codes
+    # of one information bit ((3,2), (3,3), (4,4), (4,7)), of 2t + 1 = n ((3,3), (4,7)) and of a
+    # true distance above the designed one ((5,4): the generator of (5,5))
+    (2, 1, 5, 64, 3.0),
+    (3, 1, 5, 64, 3.0), (3, 2, 5, 64, 3.0), (3, 3, 5, 64, 3.0),
+    (4, 1, 5, 64, 3.0), (4, 3, 5, 64, 3.0), (4, 4, 5, 64, 3.0), (4, 7, 5, 32, 3.0),
+    (5, 1, 5, 64, 4.0), (5, 4, 5, 64, 4.0), (5, 6, 5, 64, 4.0),
+]
+# The same with the J = 15 build (oracle/_ref/ref_golden_j15): files vecj15_*, which
+# vectors_*'s readers (J = infinity) do not match. Lowest and top t of every remaining kernel
+# set. Every fixture of a set with TMAX > 8 holds at least two words of more than 8 * 64
+# decodes (past chunk_limit, where the cooperative kernel takes over), except (5,15): of this
+# repetition code with 2t + 1 = n no word took more than 512 decodes in 20 000 reference words
+# at each of -20, -10, -5, 0 and 5 dB, 40 000 at -60 and -40 dB and 60 000 at -30 dB (maximum
+# 481, at -30 dB), so the condition is unmet there; it is recorded at a noisy point and the
+# hand-off of its kernel set is covered by (5,9) .. (5,12).
+# (6,31), the other such code, passes 512 decodes in about one word of 800 at -12 dB (6 of 4096
+# words of seeds 1 .. 8; maximum 2134): seed 244 is the first of seeds 1 .. 900 whose first 32
+# words hold two of them (words 13 and 24).
+# <7,32>: the reference did not finish 16 words of (7,32) in 25 s at 11, 13 or 15 dB (nor at
+# 7 or 9 dB), so t = 32 is pinned by the algebraic-decoder fixture alone and the Kaneko
+# fixtures of the set are t = 17 and t = 31.
+VECTORS_J15 = [
+    (5, 8, 5, 32, 4.0), (5, 9, 5, 32, 4.0), (5, 15, 5, 64, -10.0),
+    (6, 1, 5, 32, 5.0), (6, 7, 5, 32, 3.0), (6, 12, 5, 32, 5.0), (6, 13, 5, 32, 5.0), (6, 31, 244, 32, -12.0),
+    (7, 1, 5, 16, 4.0), (7, 8, 5, 16, 3.5), (7, 9, 5, 16, 3.5), (7, 16, 5, 16, 5.5), (7, 17, 5, 16, 5.5),
+    (7, 31, 5, 16, 8.0),
+    (8, 1, 5, 16, 2.0), (8, 16, 5, 16, 4.5), (8, 17, 5, 16, 4.0), (8, 32, 5, 16, 7.5),
 ]
 ALGDEC = [(4, 2, "exhaustive", 0, 0), (5, 3, "exhaustive", 0, 0),
-          (6, 6, "random", 20000, 31), (8, 15, "random", 3000, 37)]
+          (6, 6, "random", 20000, 31), (8, 15, "random", 3000, 37),
+          (2, 1, "exhaustive", 0, 0), (3, 1, "exhaustive", 0, 0), (3, 3, "exhaustive", 0, 0),
+          (4, 3, "exhaustive", 0, 0),
+          (5, 15, "random", 2500, 41), (6, 12, "random", 2500, 43), (6, 31, "random", 2500, 47),
+          (7, 16, "random", 2500, 53), (7, 32, "random", 2500, 59), (8, 16, "random", 2000, 61),
+          (8, 32, "random", 2000, 67)]
 SWEEPS = [(4, 2, 10000, 10000), (5, 3, 10000, 100)]
 
 
@@ -50,14 +84,29 @@ def run(args, cwd=None):
     return subprocess.run(args, check=True, capture_output=True, text=True, cwd=cwd).stdout
 
 
+def vector_jobs():
+    """(fixture file name, reference command) of every Kaneko vectors fixture."""
+    jobs = []
+    for exe, prefix, rows in (("ref_golden", "vectors", VECTORS), ("ref_golden_j15", "vecj15", VECTORS_J15)):
+        for m, t, seed, count, snr in rows:
+            jobs.append((f"{prefix}_m{m}t{t}_s{seed}_snr{snr:g}.txt.gz",
+                         [os.path.join(REF, exe), "vectors", str(m), str(t), str(seed), str(count), repr(snr)]))
+    return jobs
+
+
+def algdec_jobs():
+    """(fixture file name, reference command) of every algebraic-decoder fixture."""
+    return [(f"algdec_m{m}t{t}_{what}.txt.gz",
+             [os.path.join(REF, "ref_golden"), "algdec", str(m), str(t), what, str(count), str(seed)])
+            for m, t, what, count, seed in ALGDEC]
+
+
 def kaneko():
-    if not os.path.exists(os.path.join(REF, "ref_golden")):
+    if not all(os.path.exists(os.path.join(REF, exe)) for exe in ("ref_golden", "ref_golden_j15")):
         sys.exit("build the reference first: make -C oracle ref")
     os.makedirs(GOLD, exist_ok=True)
-    for m, t, seed, count, snr in VECTORS:
-        out = run([os.path.join(REF, "ref_golden"), "vectors", str(m), str(t), str(seed),
-                   str(count), repr(snr)])
-        name = f"vectors_m{m}t{t}_s{seed}_snr{snr:g}.txt.gz"
+    for name, args in vector_jobs() + algdec_jobs():
+        out = run(args)
         with gzip.open(os.path.join(GOLD, name), "wt") as f:
             f.write(out)
         print(name, len(out))
@@ -65,13 +114,6 @@ def kaneko():
                "/root/reference/in/infile.txt"])
     with open(os.path.join(GOLD, "infile_m6t6.txt"), "w") as f:
         f.write(out.replace("/root/reference/in/infile.txt", "in/infile.txt"))
-    for m, t, what, count, seed in ALGDEC:
-        out = run([os.path.join(REF, "ref_golden"), "algdec", str(m), str(t), what,
-                   str(count), str(seed)])
-        name = f"algdec_m{m}t{t}_{what}.txt.gz"
-        with gzip.open(os.path.join(GOLD, name), "wt") as f:
-            f.write(out)
-        print(name, len(out))
     # CLI modes 1 and 3 of src/main.cpp (stdout), and the mode-3 input itself (data)
     for args, name in ((["6", "6", "0.0", "/root/reference/in/infile.txt"], "cli_infile_m6t6.txt"),
                        (["6", "6", "3.0"], "cli_random_m6t6_snr3.txt"),

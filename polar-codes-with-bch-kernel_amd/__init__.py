@@ -36,7 +36,7 @@ EXPORTS = (
     "bchk_profile_read", "bchk_profile_read_stages", "bchk_path_counts", "bchk_tail_count",
     "bchk_tail_stats", "bchk_coop_stats", "bchk_tail_diag_read", "bchk_tail_prof_read", "bchk_set_fast_path", "bchk_set_analytic",
     "bchk_set_chunk_limit", "bchk_set_syndrome_table",
-    "bchk_syndrome_table_query", "bchk_syndrome_table_info", "bchk_polar_create", "bchk_polar_create_kdir",
+    "bchk_syndrome_table_query", "bchk_syndrome_table_info", "bchk_kernel_info", "bchk_polar_create", "bchk_polar_create_kdir",
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
     "bchk_polar_scratch_bytes", "bchk_polar_encode_device", "bchk_polar_generate_device",
@@ -139,6 +139,7 @@ def lib():
     L.bchk_syndrome_table_query.argtypes = [i32, i32, vp, sz, vp, vp]
     L.bchk_syndrome_table_info.argtypes = [i32, i32, C.POINTER(u64), C.POINTER(u64),
                                            C.POINTER(C.c_uint32)]
+    L.bchk_kernel_info.argtypes = [i32, i32, C.POINTER(C.c_int32)]
     L.bchk_path_counts.argtypes = [vp, C.POINTER(u64), C.POINTER(u64)]
     L.bchk_tail_count.argtypes = [vp, C.POINTER(u64)]
     L.bchk_tail_stats.argtypes = [vp, C.POINTER(u64)]
@@ -565,6 +566,17 @@ def syndrome_table_info(m, t):
     k, b, p = C.c_uint64(), C.c_uint64(), C.c_uint32()
     _check(lib().bchk_syndrome_table_info(m, t, C.byref(k), C.byref(b), C.byref(p)))
     return k.value, b.value, p.value
+
+
+KERNEL_INFO_FIELDS = ("tmax", "fast", "lane", "selection", "table", "tail")
+
+
+def kernel_info(m, t):
+    """The kernels a context for (m, t) would launch (bchk_kernel_info, no GPU): a dict of
+    KERNEL_INFO_FIELDS. BchkError where bchk_create refuses (m, t)."""
+    out = (C.c_int32 * 8)()
+    _check(lib().bchk_kernel_info(m, t, out))
+    return dict(zip(KERNEL_INFO_FIELDS, (int(v) for v in out)))
 
 
 def kernel_ebch(power):

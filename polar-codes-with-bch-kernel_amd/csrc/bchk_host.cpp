@@ -920,12 +920,36 @@ static void read_knobs(bchk_ctx *c) {
     c->verbose = env_flag("BCHK_VERBOSE");
 }
 
-int bchk_create(int m, int t, int J, double decoder_snr_db, int device, bchk_ctx **out) {
-    if (!out) return fail(BCHK_EINVAL, "out is NULL");
-    *out = nullptr;
+// The (m, t) pairs bchk_create accepts (and bchk_kernel_info describes).
+static int check_code(int m, int t) {
     if (m < 2 || m > kMaxM) return fail(BCHK_EINVAL, "m=%d unsupported (2..%d)", m, kMaxM);
     if (t <= 0 || t >= (1 << (m - 1)) || t > kMaxT)
         return fail(BCHK_EINVAL, "t=%d invalid for m=%d (1 <= t < 2^(m-1), t <= %d)", t, m, kMaxT);
+    return 0;
+}
+
+int bchk_kernel_info(int m, int t, int32_t out[8]) {
+    if (!out) return fail(BCHK_EINVAL, "out is NULL");
+    if (int rc = check_code(m, t)) return rc;
+    KernelSet ks{};
+    if (!select_kernels(m, t, &ks)) return fail(BCHK_EINVAL, "no kernel instantiated for m=%d t=%d", m, t);
+    FastFn fast = nullptr, lane = nullptr;
+    const bool has_fast = select_fast(m, t, &fast);
+    const bool has_lane = m >= 7 && has_fast && select_lane(m, t, &lane);
+    out[0] = ks.tmax;
+    out[1] = has_fast ? 1 : 0;
+    out[2] = has_lane ? 1 : 0;
+    out[3] = (m >= 7 && has_fast && ks.first_sel) ? 1 : 0;
+    out[4] = (syndtab_feasible(m, t) && ks.search_tab) ? 1 : 0;  // ensure_table and launch_pipe's tabk
+    out[5] = ks.tail ? 1 : 0;
+    out[6] = out[7] = 0;
+    return 0;
+}
+
+int bchk_create(int m, int t, int J, double decoder_snr_db, int device, bchk_ctx **out) {
+    if (!out) return fail(BCHK_EINVAL, "out is NULL");
+    *out = nullptr;
+    if (int rc = check_code(m, t)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return fail(BCHK_ENODEV, "no HIP device visible (libbchk has no CPU fallback)");

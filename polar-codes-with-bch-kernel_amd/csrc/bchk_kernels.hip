@@ -1727,6 +1727,7 @@ static KernelSet make_set() {
     }
     k.coop_threads = kWaveSize * coop_waves<M>();
     k.long_job_bytes = Geo<M>::NW > 1 ? sizeof(JobData<M, TMAX>) : 0;
+    k.first_sel = first_sel_capable<M, TMAX>();  // launch_first_impl's choice
     k.coop_bytes = coop;
     k.alg = &launch_alg_impl<M, TMAX>;
     k.tmax = TMAX;

@@ -32,6 +32,7 @@ struct KernelSet {
     size_t tail_block_bytes;  // the block's helper-job control (HelpCtl) after the waves
     int coop_threads;         // the cooperative kernel's workgroup size
     size_t long_job_bytes;    // m >= 7: one job's data (SearchParams::long_jobs), 0 otherwise
+    bool first_sel;           // m >= 7: the first kernel has a selection variant (no stats record)
 };
 
 typedef hipError_t (*FastFn)(const SearchParams &, size_t, hipStream_t);

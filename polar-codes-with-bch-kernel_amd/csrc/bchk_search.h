@@ -2069,7 +2069,9 @@ __device__ void search_codeword(const SearchParams &p, const uint8_t *ex, const 
             }
             ++chunks;
             const uint64_t okm = ballot(ok[g]);
-            if (base == 0 && !(okm & 1ull)) S.firstOK = false;  // :371
+            // :371; long codes without kaneko_first_kernel: first_patterns has decided it, and
+            // pattern 0 may be skipped here (skey: it re-finds the best codeword)
+            if (base == 0 && !(okm & 1ull) && (NW == 1 || p.queue)) S.firstOK = false;
             // Only improvements (l < l0) change the state: m0 at an improvement is the fixed
             // i = 0 value or, once i = 0 has failed, the improving candidate's own m (:374),
             // and l0 only decreases, so successes with l >= l0 can be skipped wholesale. The

@@ -74,6 +74,11 @@ def vector_files():
     return sorted(glob.glob(os.path.join(GOLD, "vectors_*.txt.gz")))
 
 
+def vector_j15_files():
+    """Vectors of the reference's J = 15 build (decode them with J = 15)."""
+    return sorted(glob.glob(os.path.join(GOLD, "vecj15_*.txt.gz")))
+
+
 @dataclass
 class AlgDec:
     name: str
@@ -97,7 +102,7 @@ def load_algdec(path):
             ok.append(int(p[2]))
             a = _bits(p[3], n)
             ans.append(a if a is not None else np.zeros(n, np.uint8))
-    m = {15: 4, 31: 5, 63: 6, 255: 8}[n]
+    m = {3: 2, 7: 3, 15: 4, 31: 5, 63: 6, 127: 7, 255: 8}[n]
     return AlgDec(os.path.basename(path), m, t, n, np.array(words, np.uint8),
                   np.array(ok, np.uint8), np.array(ans, np.uint8))
 
