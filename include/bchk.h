@@ -294,7 +294,18 @@ typedef struct bchk_polar bchk_polar;
  * (out/external/MixedKernelListDecoder.cpp:9): spec is the text of the reference's code
  * specification (out/external/MixedKernelEncoder.cpp:7-98: "N K d layers #shortened
  * #punctured", kernel names, shortened / punctured symbols, U - K freezing constraints).
- * Kernels: Arikan ("A") layers, and matrix kernels ("-file" / "<file", a size and size^2
+ * Kernels: Arikan ("A") layers; the library's named kernels "G" (3 x 3, rows 100 / 110 / 011)
+ * and "A5" (5 x 5, rows 10000 / 11000 / 10100 / 10001 / 11110: what CA5Kernel::Multiply
+ * computes, TruncatedArikanKernel.cpp:204-216 -- the A5[] array at :251-258 has the last two
+ * rows exchanged and is not what the library encodes or decodes with), names in any case as
+ * Kernel.cpp:234-274 compares them, decoded by the library's own recursive f/g processors
+ * (TruncatedArikanKernel.cpp:152-184, :341-397), whose per-path state (one float per element
+ * for G; three floats and a bit for A5) is carried with the path through clones and
+ * suspended launches. The reference itself copies G's state on a clone only at phase 0 of
+ * the whole code (:141-149, KernelListEngine.cpp:361), so with list_size > 1 its output is
+ * defined only where every G is the innermost layer; there, and at list_size 1, and for A5
+ * anywhere, the lists are the reference's bit for bit, and elsewhere they are those of the
+ * state travelling with the path. And matrix kernels ("-file" / "<file", a size and size^2
  * entries, Kernel.cpp:93-107 -- e.g. BCH-derived kernels) of size <= 64, whose kernel LLRs are
  * the trellis min-sum of out/external/TrellisKernelProcessor.cpp:234-294 (polar_mixed.hip):
  * coset enumeration below 16, the trellis for 16..32 (at most 2^12 states per depth), and an
@@ -487,6 +498,9 @@ int bchk_kernel_write_file(const char *path, const uint8_t *K, int l, const uint
  * capacities far below 1e-16 that inner layers see (a sampled table's difference is clamped
  * at 0); every capacity is finite and in [0, 1]. The K largest capacities carry information, ties going to
  * the higher index. cap (may be NULL) receives the U capacities; spec receives the text
+ * (a named kernel "G" / "A5" in `layers` is BCHK_EINVAL with a message naming it: the
+ * library's tables for them are program text, and ML polarisation of the matrix is not what
+ * A5's f/g processor achieves; bchk_polar_design_genie takes them)
  * "U K 0 n 0 0", the layer line and "1 f" per frozen symbol, ascending (no shortening,
  * puncturing or dynamic freezing). *needed = the bytes the text takes with its terminator
  * (0 when the arguments were rejected before it was formed); a buffer shorter than that is
@@ -499,7 +513,8 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
  * with the TRUE u_0..u_{phi-1} (the encoder's inputs, rebuilt from the sent information bits as
  * bchk_polar_generate_device's encoder forms them) fed back: LLR_phi is, bit for bit, the value
  * bchk_polar_decode_device computes for a path whose earlier decisions were u_0..u_{phi-1}
- * (LoadLLRs with 100000 at shortened and 0 at punctured symbols, f/g on Arikan layers, coset
+ * (LoadLLRs with 100000 at shortened and 0 at punctured symbols, f/g on Arikan layers, the
+ * named kernels' processors on "G" / "A5" layers, coset
  * enumeration or the trellis on matrix layers under the context's per-layer choice,
  * BCHK_POLAR_TRELLIS). Per symbol phi = 0..U-1, frozen symbols included, and per word:
  *   err[phi]  += 1 when (LLR_phi < 0 ? 1 : 0) != u_phi            (the decoder's decision rule)

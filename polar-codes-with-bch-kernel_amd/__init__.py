@@ -407,8 +407,13 @@ class KanekoKernelProcessor:
 class PolarListDecoder:
     """CMixedKernelListDecoder(Spec, ListSize) + Decode (out/external/MixedKernelListDecoder.cpp
     :9, :211-268) on the GPU: batched SC-list decoding of a polar code given by the
-    reference's specification text (Arikan layers), and the AWGN/BPSK simulation around it
-    (encode_device, generate_device, count_device, sweep_device: out/external/Simulator.cpp)."""
+    reference's specification text, and the AWGN/BPSK simulation around it (encode_device,
+    generate_device, count_device, sweep_device: out/external/Simulator.cpp). Layers: "A"
+    (Arikan), matrix files ("-file"), and the library's named kernels "G" (3 x 3) and "A5"
+    (5 x 5, rows as CA5Kernel::Multiply computes them), in any case, decoded by their own f/g
+    processors with the state carried per path: code lengths such as 12, 24, 40, 60, 96. With
+    L > 1 the lists are the reference's bit for bit where the reference is defined (every G
+    the innermost layer; A5 anywhere), see include/bchk.h and DESIGN 5.14."""
 
     def __init__(self, spec, L, device=0, kernel_dir=None):
         h = C.c_void_p()
@@ -695,7 +700,8 @@ def write_kernel_file(path, K, counts=None):
 def design_bec(layers, K, capacity=0.5, kernel_dir=None, samples=1 << 16, seed=1, device=0):
     """BEC design of a polar code over the kernels of `layers` (names, or the spec's layer line):
     -> (spec text for PolarListDecoder, capacities [U] of the symbols). Matrix kernels take
-    their BEC table from their file, or from the GPU when the file has none."""
+    their BEC table from their file, or from the GPU when the file has none. The named
+    kernels "G" / "A5" are refused (BchkError naming the kernel): use design_genie."""
     line = layers if isinstance(layers, str) else " ".join(layers)
     cap = np.zeros(16384, np.float64)
     buf = C.create_string_buffer(64 + len(line) + 8 * 16384)
@@ -709,7 +715,8 @@ def design_bec(layers, K, capacity=0.5, kernel_dir=None, samples=1 << 16, seed=1
 def design_genie(layers, K, snr_db, words, kernel_dir=None, seed=1, device=0):
     """Monte-Carlo AWGN design over the kernels of `layers`: the symbols ranked by their genie-aided
     error counts over `words` words of the stream `seed` at Eb/N0 snr_db (ties: the larger soft sum,
-    then the higher index) -> (spec text for PolarListDecoder, err [U] u64, soft [U] i64)."""
+    then the higher index) -> (spec text for PolarListDecoder, err [U] u64, soft [U] i64).
+    Layers may be "A", matrix files, and the named kernels "G" and "A5"."""
     line = layers if isinstance(layers, str) else " ".join(layers)
     err = np.zeros(16384, np.uint64)
     soft = np.zeros(16384, np.int64)

@@ -16,6 +16,7 @@
 // matrix layers (design_row below): it is accurate only for capacities near 1/2. The tables
 // themselves come from csrc/kernel_bec.hip.
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -156,6 +157,14 @@ int read_kernel_file(const std::string &name, const char *kdir, int *size, std::
     return BCHK_OK;
 }
 
+// the size of a kernel the library names besides "A" (Kernel.cpp:253-274, any case): "G" 3,
+// "A5" 5 (TruncatedArikanKernel.cpp), else 0
+int named_kernel_size(const std::string &name) {
+    std::string low = name;
+    for (char &ch : low) ch = (char)tolower((unsigned char)ch);
+    return low == "g" ? 3 : low == "a5" ? 5 : 0;
+}
+
 bool invertible(const std::vector<uint8_t> &K, int l) {
     std::vector<uint64_t> a(l, 0);
     for (int r = 0; r < l; ++r)
@@ -260,6 +269,11 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
                 seen[name.substr(1)] = j;
             }
             U *= L[j].l;
+        } else if (named_kernel_size(name)) {
+            // the library's BEC table of a named kernel is program text, and the ML polarisation
+            // of its matrix is not what its f/g processor achieves (A5): no BEC design here
+            return dfail(BCHK_EINVAL, "BEC design does not take the named kernel %s (its decoder is an f/g processor, "
+                                      "not ML over the matrix); use bchk_polar_design_genie", name.c_str());
         } else {
             return dfail(BCHK_EINVAL, "Unknown kernel %s", name.c_str());
         }
@@ -319,6 +333,8 @@ int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double 
             if (int rc = read_kernel_file(name, kdir, &l, Km, tab, &has)) return rc;
             if (!invertible(Km, l)) return dfail(BCHK_EINVAL, "Kernel is singular (%s)", name.c_str() + 1);
             U *= l;
+        } else if (named_kernel_size(name)) {
+            U *= named_kernel_size(name);
         } else {
             return dfail(BCHK_EINVAL, "Unknown kernel %s", name.c_str());
         }

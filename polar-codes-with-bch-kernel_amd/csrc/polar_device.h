@@ -74,6 +74,15 @@ static_assert(kMlOffU % 8 == 0 && kMlHeadBytes % 4 == 0 && kMlNodeBytes % 4 == 0
 // (state | z << 13 | valid << 14).
 constexpr int kPolarTrellisMaxBits = 12;
 constexpr uint32_t kTrellisZ = 1u << 13, kTrellisValid = 1u << 14, kTrellisState = kTrellisZ - 1u;
+// The named kernels "G" (3 x 3) and "A5" (5 x 5) of TruncatedArikanKernel.cpp are matrix layers
+// for the encoder and the partial sums (their rows), but take their LLRs from the library's
+// own recursive f/g processors (pllr::named_llrs), which keep a state per path and element
+// from one phase to the next: G one float (L1 [+] L2) at foff[j] + s; A5 three floats L04, L13,
+// L024 at foff[j] + {0, d, 2d} + s (d = outer[j + 1]) and one bit at ooff[j] + s. The floats
+// lie in the path's S stride past its layers, the bit in its offset-state stride: what a path
+// clone copies and a save slot covers.
+constexpr uint8_t kNamedG = 1, kNamedA5 = 2;
+constexpr int polar_named_floats(int kind) { return kind == kNamedG ? 1 : kind == kNamedA5 ? 3 : 0; }
 struct PolarMixedParams {
     const float *llr;
     uint8_t *info, *cw;
@@ -95,6 +104,8 @@ struct PolarMixedParams {
     uint8_t arikan[kPolarMaxLayers];
     uint8_t trellis[kPolarMaxLayers];  // matrix layer decoded through its trellis
     uint8_t ml[kPolarMaxLayers];       // matrix layer decoded by the ordered-statistics search
+    uint8_t named[kPolarMaxLayers];    // kNamedG / kNamedA5: the f/g processor of a named kernel
+    int32_t foff[kPolarMaxLayers];     // a named layer's float state in the path's S stride
     int32_t any_ml;                    // LDS holds the search scratch
     // Time-budgeted launches (round 6; codes with search layers): a wave past `budget` ticks
     // of the 100 MHz clock since its launch began suspends its codeword between two search
@@ -234,6 +245,8 @@ struct PolarGenieParams {
     int32_t outer[kPolarMaxLayers + 1];
     int32_t soff[kPolarMaxLayers + 1], coff[kPolarMaxLayers + 1], ooff[kPolarMaxLayers];
     uint8_t arikan[kPolarMaxLayers], trellis[kPolarMaxLayers];
+    uint8_t named[kPolarMaxLayers];  // as in PolarMixedParams
+    int32_t foff[kPolarMaxLayers];
 };
 // LDS of one wave: channel LLRs, S, C, offset states, kernel rows, the trellis metric buffers
 // (2 x tstates floats), the packed information bits and the packed u

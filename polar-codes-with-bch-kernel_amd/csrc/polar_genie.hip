@@ -9,7 +9,8 @@
 // wave rebuilds u from the sent information bits exactly as polar_gen_kernel does
 // (polar_enc_device.h), keeps it packed in LDS, then runs the decoder's phase loop over the
 // mixed layout: LoadLLRs, IterativelyCalcS with the routines of polar_llr_device.h (the f/g of
-// Arikan layers, coset enumeration or the trellis Viterbi of matrix layers -- the code
+// Arikan layers, coset enumeration or the trellis Viterbi of matrix layers, the f/g processors
+// of the named G / A5 layers -- the code
 // polar_mixed_kernel runs, so LLR_φ is its value bit for bit for a path whose earlier decisions
 // were u_0..u_{φ-1}), then IterativelyUpdateC with the true u_φ. Lane φ & 63 keeps LLR_φ in a
 // register; every 64 phases (and at the end) the wave stores one coalesced row segment.
@@ -48,6 +49,7 @@ __global__ void __launch_bounds__(64) polar_genie_kernel(PolarGenieParams p) {
     auto Sof = [&](int, int lam) -> float * { return lam == 0 ? chan : S + p.soff[lam]; };
     auto Cof = [&](int, int lam) -> uint8_t * { return C + p.coff[lam]; };
     auto Oof = [&](int, int j) -> uint8_t * { return O + p.ooff[j]; };
+    auto Fof = [&](int, int j) -> float * { return S + p.foff[j]; };  // named layers' state
     auto pathof = [](int) -> int { return 0; };  // one path
     const pllr::Trellis tr{p.tent, p.tbase, p.tlog, reinterpret_cast<float *>(gsm + lo.o_tm), p.tstates};
     const int lastsz = t.ksize[nl - 1];
@@ -81,6 +83,11 @@ __global__ void __launch_bounds__(64) polar_genie_kernel(PolarGenieParams p) {
                 const int d = p.outer[j + 1], l = t.ksize[j];
                 if (p.arikan[j]) {
                     pllr::arikan_llrs(j, loc, d, d, lane, pathof, Sof, Cof);
+                    wsync();
+                    continue;
+                }
+                if (p.named[j]) {
+                    pllr::named_llrs(p.named[j], j, loc, d, d, lane, pathof, Sof, Cof, Fof, Oof);
                     wsync();
                     continue;
                 }

@@ -89,10 +89,11 @@ struct PBuf {
 struct bchk_polar {
     int N = 0, K = 0, U = 0, n = 0, L = 0, device = 0;
     // layers: kernel size, Arikan flag, rows as bitmasks (bit c = K[r][c]); mixed = any
-    // matrix layer (decoded by polar_mixed_kernel)
+    // matrix or named (G / A5) layer (decoded by polar_mixed_kernel)
     bool mixed = false;
     std::vector<int> ksize;
     std::vector<uint8_t> arikan;
+    std::vector<uint8_t> named;   // kNamedG / kNamedA5 (polar_device.h), 0 otherwise
     std::vector<uint64_t> krows;  // [layer][kPolarMaxKernel]
     PolarMixedParams mp{};        // the mixed layout (sizes, offsets)
     size_t off_krows = 0;
@@ -138,16 +139,32 @@ PolarMixedLayout mixed_lds(const bchk_polar *c) {
 
 // The specification (MixedKernelEncoder.cpp:7-98): header, kernel names, shortened and
 // punctured symbols, then U - K freezing constraints "w t_1 ... t_w" (ascending, the frozen
-// symbol last). The GPU decoder takes Arikan layers ("A"); other kernels are rejected.
-// GetKernelByName (Kernel.cpp:235-252): "A" (any case), or a matrix file "-path" / "<path"
-// (relative to kdir) holding the size and size^2 entries (Kernel.cpp:93-107); the kernel must
-// be invertible (Kernel.cpp:155-176).
-int read_kernel(const std::string &name, const char *kdir, int *size, uint64_t *rows, bool *arikan) {
-    if (name == "A" || name == "a") {
+// symbol last).
+// GetKernelByName (Kernel.cpp:235-274): "A", "G" or "A5" (any case, _stricmp), or a matrix
+// file "-path" / "<path" (relative to kdir) holding the size and size^2 entries
+// (Kernel.cpp:93-107); the kernel must be invertible (Kernel.cpp:155-176). *named: kNamedG /
+// kNamedA5 for the kernels of TruncatedArikanKernel.cpp, decoded by their own f/g processors.
+// Their rows are what CGKernel::Multiply (:18-30) and CA5Kernel::Multiply (:204-216) compute,
+// which is what the library encodes and decodes with. For A5 that is the matrix of the
+// file's comment (:193-197), rows 10000 / 11000 / 10100 / 10001 / 11110; the A5[] array
+// GetKernel() returns (:251-258) has the last two rows the other way round and is not used.
+int read_kernel(const std::string &name, const char *kdir, int *size, uint64_t *rows, bool *arikan, uint8_t *named) {
+    std::string low = name;
+    for (char &ch : low) ch = (char)tolower((unsigned char)ch);
+    *named = 0;
+    if (low == "a") {
         *size = 2;
         rows[0] = 1u;       // 1 0
         rows[1] = 3u;       // 1 1  (Kernel.cpp:8-12)
         *arikan = true;
+        return 0;
+    }
+    if (low == "g" || low == "a5") {
+        static const uint64_t g3[3] = {1u, 3u, 6u}, a5[5] = {1u, 3u, 5u, 17u, 15u};  // bit c = K[r][c]
+        *size = low == "g" ? 3 : 5;
+        for (int r = 0; r < *size; ++r) rows[r] = low == "g" ? g3[r] : a5[r];
+        *arikan = false;
+        *named = low == "g" ? kNamedG : kNamedA5;
         return 0;
     }
     if (name.empty() || (name[0] != '-' && name[0] != '<')) return pfail(BCHK_EINVAL, "Unknown kernel %s", name.c_str());
@@ -306,13 +323,16 @@ int parse_spec(bchk_polar *c, const char *spec, const char *kdir) {
     if (layers < 1 || layers > kPolarMaxLayers) return pfail(BCHK_EINVAL, "%d layers unsupported", layers);
     c->ksize.assign(layers, 2);
     c->arikan.assign(layers, 1);
+    c->named.assign(layers, 0);
     c->krows.assign((size_t)layers * kPolarMaxKernel, 0ull);
     long Ul = 1;
     for (int i = 0; i < layers; ++i) {
         std::string name;
         if (!(in >> name)) return pfail(BCHK_EINVAL, "missing kernel name %d", i);
         bool ar = false;
-        if (int rc = read_kernel(name, kdir, &c->ksize[i], &c->krows[(size_t)i * kPolarMaxKernel], &ar)) return rc;
+        if (int rc = read_kernel(name, kdir, &c->ksize[i], &c->krows[(size_t)i * kPolarMaxKernel], &ar,
+                                 &c->named[i]))
+            return rc;
         c->arikan[i] = ar ? 1 : 0;
         c->mixed = c->mixed || !ar;
         Ul *= c->ksize[i];
@@ -392,7 +412,11 @@ int parse_spec(bchk_polar *c, const char *spec, const char *kdir) {
     return 0;
 }
 
-// the mixed layout of one path (oracle/polar_oracle.c plr_decode's offsets)
+// the mixed layout of one path (oracle/polar_oracle.c plr_decode's offsets). A named layer
+// (G / A5) has no offset state; its processor's float state follows the S layers in the path's
+// S stride and A5's bit takes the layer's place in the offset-state stride (polar_device.h).
+// With such a layer the S stride gets polar_path_s's 16 bytes of padding: the state is read
+// and written at stride d across the lanes, like S, one path after the other.
 void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
     const int nl = c->n;
     m.nl = nl;
@@ -400,14 +424,26 @@ void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
     for (int j = 0; j < nl; ++j) {
         m.ksize[j] = c->ksize[j];
         m.arikan[j] = c->arikan[j];
+        m.named[j] = c->named[j];
         m.outer[j + 1] = m.outer[j] / c->ksize[j];
     }
     int so = 0, co = 0, oo = 0;
     for (int lam = 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
     for (int lam = 0; lam <= nl; ++lam) { m.coff[lam] = co; co += lam ? m.outer[lam] * c->ksize[lam - 1] : m.outer[0]; }
-    for (int j = 0; j < nl; ++j) { m.ooff[j] = oo; if (!c->arikan[j]) oo += c->ksize[j] * m.outer[j + 1]; }
+    bool any_named = false;
+    for (int j = 0; j < nl; ++j) {
+        m.ooff[j] = oo;
+        m.foff[j] = so;
+        if (c->named[j]) {
+            any_named = true;
+            so += polar_named_floats(c->named[j]) * m.outer[j + 1];
+            if (c->named[j] == kNamedA5) oo += m.outer[j + 1];
+        } else if (!c->arikan[j]) {
+            oo += c->ksize[j] * m.outer[j + 1];
+        }
+    }
     m.soff[0] = 0;
-    m.ssize = (so + 3) & ~3;
+    m.ssize = ((so + 3) & ~3) + (any_named ? 4 : 0);
     m.csize = (co + 15) & ~15;
     m.osize = (oo + 15) & ~15;
 }
@@ -460,9 +496,10 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         c->tlog.assign((size_t)nl * kPolarMaxKernel * (kPolarMaxKernel + 1), 0u);
         c->tent.clear();
         for (int j = 0; j < nl; ++j) {
-            m.ml[j] = (!c->arikan[j] && c->ksize[j] >= std::min(mlmin, kPolarMaxTrellisKernel + 1)) ? 1 : 0;
+            const bool matrix = !c->arikan[j] && !c->named[j];  // LLRs over the coset of its rows
+            m.ml[j] = (matrix && c->ksize[j] >= std::min(mlmin, kPolarMaxTrellisKernel + 1)) ? 1 : 0;
             m.any_ml |= m.ml[j];
-            m.trellis[j] = (!c->arikan[j] && !m.ml[j] && c->ksize[j] >= tmin) ? 1 : 0;
+            m.trellis[j] = (matrix && !m.ml[j] && c->ksize[j] >= tmin) ? 1 : 0;
             if (!m.trellis[j]) continue;
             const int most = build_trellis(&c->krows[(size_t)j * kPolarMaxKernel], c->ksize[j], c->tent,
                                            &c->tbase[(size_t)j * kPolarMaxKernel],
@@ -915,6 +952,8 @@ static int genie_setup(bchk_polar *c) {
         g.ooff[j] = m.ooff[j];
         g.arikan[j] = m.arikan[j];
         g.trellis[j] = m.trellis[j];
+        g.named[j] = m.named[j];
+        g.foff[j] = m.foff[j];
     }
     const size_t lds = polar_genie_layout(c->U, c->K, g.ssize, g.csize, g.osize, c->n, g.tstates).bytes;
     if (lds > 160 * 1024)

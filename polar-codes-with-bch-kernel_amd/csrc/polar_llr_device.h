@@ -6,8 +6,9 @@
 // CTrellisKernelProcessor::GetLLRs (out/external/TrellisKernelProcessor.cpp:234-294): the
 // offset state accumulates the known kernel inputs times their rows, and the LLR of input
 // `phase` is the min-sum difference best[1] - best[0] over the coset of the remaining rows,
-// by coset enumeration or by the pull-form Viterbi over the trellis. Partial sums:
-// IterativelyUpdateC (KernelListEngine.cpp:266-315).
+// by coset enumeration or by the pull-form Viterbi over the trellis. Named layers (G, A5):
+// the recursive f/g processors of TruncatedArikanKernel.cpp with their per-path state. Partial
+// sums: IterativelyUpdateC (KernelListEngine.cpp:266-315).
 //
 // The routines run on one wave. Work items are (path, element) pairs, it = k * d + s with k
 // an index into the caller's active paths: pathof(k) is the path, Sof(q, λ) its LLRs of layer
@@ -66,6 +67,77 @@ __device__ __forceinline__ void arikan_llrs(int j, int loc, int d, int tot, int 
             r = __uint_as_float(__float_as_uint(mn) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
         }
         dst[s] = r;
+    }
+}
+
+// SoftXOR and SoftCombine of one element (SoftProcessing.cpp:54-80, :39-50), spelled as above
+__device__ __forceinline__ float soft_xor(float a, float b) {
+    const float fa = fabsf(a), fb = fabsf(b), mn = fa < fb ? fa : fb;
+    return __uint_as_float(__float_as_uint(mn) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
+}
+__device__ __forceinline__ float soft_combine(float a, float b, uint32_t c) { return c ? b - a : b + a; }
+
+// Named layer j (kind kNamedG / kNamedA5, polar_device.h) at local phase loc:
+// CGKernelProcessor::GetLLRs and CA5KernelProcessor::GetLLRs (out/external/
+// TruncatedArikanKernel.cpp:152-184, :341-397), operation for operation. y_i = Sof(q, j)[i d + s]
+// are the layer's LLRs, u_i = Cof(q, j + 1)[i d + s] its known inputs; the state of element s
+// (Fof(q, j): floats, stride d per variable; Oof(q, j): A5's bit) is the path's own, written by
+// the lane that reads it at a later phase, so it travels with every clone of the path.
+template <class PathOf, class SOf, class COf, class FOf, class OOf>
+__device__ __forceinline__ void named_llrs(int kind, int j, int loc, int d, int tot, int lane, PathOf pathof, SOf Sof,
+                                           COf Cof, FOf Fof, OOf Oof) {
+    for (int it = lane; it < tot; it += 64) {
+        const int q = pathof(it / d), s = it % d;
+        const float *y = Sof(q, j) + s;
+        const uint8_t *u = Cof(q, j + 1) + s;
+        float *st = Fof(q, j) + s;
+        float r;
+        if (kind == kNamedG) {  // state: L1 [+] L2
+            if (loc == 0) {     // (:163-169)
+                const float l12 = soft_xor(y[d], y[2 * d]);
+                st[0] = l12;
+                r = soft_xor(y[0], l12);
+            } else if (loc == 1) {  // (:170-175)
+                r = soft_combine(y[0], st[0], u[0]);
+            } else {  // (:176-181)
+                r = soft_combine(y[d], y[2 * d], u[d]);
+            }
+        } else {  // A5; state: L04, L13, L024 and the bit pC
+            float *l04 = st, *l13 = st + d, *l024 = st + 2 * d;
+            uint8_t *pc = Oof(q, j) + s;
+            if (loc == 0) {  // (:357-364)
+                const float a = soft_xor(y[0], y[4 * d]);
+                const float b = soft_xor(a, y[2 * d]);
+                const float c = soft_xor(y[d], y[3 * d]);
+                *l04 = a;
+                *l024 = b;
+                *l13 = c;
+                r = soft_xor(b, c);
+            } else if (loc == 1) {  // (:365-369)
+                r = soft_combine(*l024, *l13, u[0]);
+            } else if (loc == 2) {  // (:370-377)
+                const uint32_t c = (u[0] ^ u[d]) & 1u;
+                const float b = soft_combine(*l04, y[2 * d], c);
+                const float e = soft_combine(y[d], y[3 * d], u[d]);
+                *pc = (uint8_t)c;
+                *l024 = b;
+                *l13 = e;
+                r = soft_xor(b, e);
+            } else if (loc == 3) {  // (:378-387)
+                const float e = soft_combine(y[2 * d], soft_combine(y[d], y[3 * d], u[d]), u[2 * d]);
+                const float a = soft_xor(y[0], e);
+                const uint32_t c = (*pc ^ u[2 * d]) & 1u;
+                *l13 = e;
+                *l04 = a;
+                *pc = (uint8_t)c;
+                r = soft_combine(a, y[4 * d], c);
+            } else {  // (:388-393)
+                const uint32_t c = (*pc ^ u[3 * d]) & 1u;
+                *pc = (uint8_t)c;
+                r = soft_combine(y[0], *l13, c);
+            }
+        }
+        Sof(q, j + 1)[s] = r;
     }
 }
 

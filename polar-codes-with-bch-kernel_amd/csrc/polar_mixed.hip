@@ -9,6 +9,9 @@
 // best[1] - best[0] over the coset of the remaining rows (each word's metric a left-to-right
 // float sum of |y| over its disagreeing positions -- the trellis's value bit for bit, see
 // oracle/polar_oracle.c). Same decisions, arithmetic and path indices as the CPU restatement.
+// Layers named G / A5 take their LLRs from the recursive f/g processors of
+// TruncatedArikanKernel.cpp:152-184, :341-397 (pllr::named_llrs); their state is part of the
+// path (in its S and offset-state strides), so clones and save slots carry it.
 //
 // Execution model: one wave per codeword (persistent). Every path's S (per layer, outer[λ]
 // floats), C (kernel inputs per layer) and matrix offset states live in LDS; lane q < L holds
@@ -358,6 +361,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     auto Sof = [&](int q, int lam) -> float * { return lam == 0 ? chan : S + (size_t)q * p.ssize + p.soff[lam]; };
     auto Cof = [&](int q, int lam) -> uint8_t * { return C + (size_t)q * p.csize + p.coff[lam]; };
     auto Oof = [&](int q, int j) -> uint8_t * { return O + (size_t)q * p.osize + p.ooff[j]; };
+    auto Fof = [&](int q, int j) -> float * { return S + (size_t)q * p.ssize + p.foff[j]; };  // named layers' state
     auto pathof = [&](int k) -> int { return (int)act[k]; };  // the k-th active path
     const pllr::Trellis tr{p.tent, p.tbase, p.tlog, tmet, p.tstates};
     const int lastsz = p.ksize[nl - 1];
@@ -460,6 +464,11 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                 const int tot = nact * d;
                 if (p.arikan[j]) {
                     pllr::arikan_llrs(j, loc, d, tot, lane, pathof, Sof, Cof);
+                    wsync();
+                    continue;
+                }
+                if (p.named[j]) {  // G / A5: the f/g processor over the path's carried state
+                    pllr::named_llrs(p.named[j], j, loc, d, tot, lane, pathof, Sof, Cof, Fof, Oof);
                     wsync();
                     continue;
                 }
