@@ -263,6 +263,10 @@ int bchk_set_chunk_limit(bchk_ctx *ctx, uint32_t chunks);
  * normalised syndrome in a table of the weight <= t coset leaders (csrc/bchk_syndtab.h)
  * instead of Berlekamp-Massey + Chien. Results are identical either way. */
 int bchk_set_syndrome_table(bchk_ctx *ctx, int enable);
+/* The resident waves of the first exact pass as the next decode call would launch it (the
+ * table setting above chooses the kernel). For n <= 63 wave g takes item g of the fast
+ * kernel's queue, and the items from `waves` upward are claimed. */
+int bchk_first_pass_waves(const bchk_ctx *ctx, uint32_t *waves);
 /* Host-side decode through that table (no GPU): for odd syndromes synd[i][0..t) =
  * S_1, S_3, ..., S_{2t-1}, ok[i] = 1 iff Decoder::decode succeeds, and err[i] (may be
  * NULL) = the flipped positions as a bit mask. BCHK_EINVAL when (m, t) has no table.

@@ -35,7 +35,7 @@ EXPORTS = (
     "bchk_stream_sync", "bchk_sweep", "bchk_sync", "bchk_stream", "bchk_profile",
     "bchk_profile_read", "bchk_profile_read_stages", "bchk_path_counts", "bchk_tail_count",
     "bchk_tail_stats", "bchk_coop_stats", "bchk_tail_diag_read", "bchk_tail_prof_read", "bchk_set_fast_path", "bchk_set_analytic",
-    "bchk_set_chunk_limit", "bchk_set_syndrome_table",
+    "bchk_set_chunk_limit", "bchk_set_syndrome_table", "bchk_first_pass_waves",
     "bchk_syndrome_table_query", "bchk_syndrome_table_info", "bchk_kernel_info", "bchk_polar_create", "bchk_polar_create_kdir",
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
@@ -119,6 +119,7 @@ def lib():
     L.bchk_profile_read.argtypes = [vp, C.POINTER(dbl), C.POINTER(u64)]
     L.bchk_set_fast_path.argtypes = [vp, i32]
     L.bchk_set_syndrome_table.argtypes = [vp, i32]
+    L.bchk_first_pass_waves.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.bchk_polar_create.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bchk_polar_create_kdir.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bchk_polar_destroy.argtypes = [vp]
@@ -402,6 +403,12 @@ class KanekoKernelProcessor:
     def set_syndrome_table(self, enable=True):
         """Syndrome decoding table of the search kernels (results identical either way)."""
         _check(lib().bchk_set_syndrome_table(self._h, 1 if enable else 0))
+
+    def first_pass_waves(self):
+        """Resident waves of the first exact pass (its queue items below that are not claimed)."""
+        w = C.c_uint32()
+        _check(lib().bchk_first_pass_waves(self._h, C.byref(w)))
+        return w.value
 
 
 class PolarListDecoder:

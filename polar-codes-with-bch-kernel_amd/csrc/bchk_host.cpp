@@ -409,6 +409,7 @@ struct bchk_ctx {
         DevBuf queue, heavy, ctrl, l1q, l1rec;  // l1q / l1rec: first pass -> analytic tail
         DevBuf pre;                             // m >= 7: the lane pre-pass's finished rows
         DevBuf jobctl, jobs;                    // m >= 7: cooperative-kernel jobs (help)
+        uint32_t last_epoch = 0;                // the launch epoch of the tags jobs may still hold
         hipStream_t s = nullptr, aux = nullptr;  // s unused for pipe 0 (the caller's stream)
         hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_done = nullptr, ev_fast = nullptr;
     };
@@ -794,17 +795,20 @@ int launch_pipe(bchk_ctx *c, bchk_ctx::Pipe &P, bool first, int variant, const d
             // A chunk record is taken as delivered when its tag equals (generation << 32 |
             // chunk + 1), the generation built from this context's 20-bit launch epoch. Tags
             // must therefore never hold a value from another context (memory hipMalloc hands
-            // back) or from the launch 2^20 epochs ago: the jobs memory is zeroed whenever it
-            // is (re)allocated and whenever the epoch's low 20 bits wrap. A zero tag matches
-            // no chunk (chunk + 1 >= 1).
+            // back) or from a launch 2^20 epochs ago: the jobs memory is zeroed whenever it
+            // is (re)allocated and whenever the epoch's low 20 bits have wrapped since this
+            // pipe's last launch (the epoch counts the context's launches, over all pipes, so
+            // a pipe need not draw the wrapping epoch itself). A zero tag matches no chunk
+            // (chunk + 1 >= 1).
             const size_t jobs_cap_before = P.jobs.cap;  // ensure() only grows it
             if ((rc = P.jobctl.ensure((size_t)(grid_coop + 1) * 128)) ||
                 (rc = P.jobs.ensure((size_t)grid_coop * c->ks.long_job_bytes)))
                 return rc;
             HIP_TRY(hipMemsetAsync(P.jobctl.p, 0, (size_t)(grid_coop + 1) * 128, cs));
             const uint32_t epoch = ++c->long_epoch;
-            if (P.jobs.cap != jobs_cap_before || (epoch & 0xFFFFFu) == 0u)
+            if (P.jobs.cap != jobs_cap_before || (epoch >> 20) != (P.last_epoch >> 20))
                 HIP_TRY(hipMemsetAsync(P.jobs.p, 0, P.jobs.cap, cs));
+            P.last_epoch = epoch;
             pc.long_jobctl = P.jobctl.p;
             pc.long_jobs = P.jobs.p;
             pc.long_help_max = c->long_help_max;
@@ -1669,6 +1673,14 @@ int bchk_diag_read(bchk_ctx *c, uint64_t *out, size_t items) {
 int bchk_set_syndrome_table(bchk_ctx *c, int enable) {
     if (!c) return fail(BCHK_EINVAL, "ctx is NULL");
     c->use_table = enable != 0;
+    return 0;
+}
+
+int bchk_first_pass_waves(const bchk_ctx *c, uint32_t *waves) {
+    if (!c || !waves) return fail(BCHK_EINVAL, "NULL argument");
+    // launch_pipe's choice of the search kernel and its persistent grid
+    const bool tabk = c->use_table && c->ks.search_tab && syndtab_feasible(c->m, c->t);
+    *waves = (uint32_t)(tabk ? c->grid_tab : c->grid) * (uint32_t)kWavesPerBlock;
     return 0;
 }
 

@@ -99,6 +99,12 @@ kaneko_search_kernel(SearchParams p) {
     if (none && !help) return;
     int x = xcc_id(), exhausted = none ? 8 : 0;
     uint32_t ndone = 0;
+    // The n <= 63 first pass over the ring kernel's queue (FP): wave gs takes item gs without
+    // an atomic, and the claims hand out the items from `stride` upward (sub-queue x holds
+    // stride + x + 8 k), so a wave's first codeword costs no claim round trip and a queue no
+    // longer than the grid costs no atomic at all.
+    constexpr bool FP = !AN && Geo<M>::NW == 1;
+    uint32_t known = 0;  // a lower bound of sub-queue x's head (the wave's own last claim + 1)
     for (;;) {
         uint32_t cw = kEmptySlot, item = 0;
 #ifdef BCHK_FP_TRACE
@@ -120,6 +126,30 @@ kaneko_search_kernel(SearchParams p) {
             cw = gs;
             item = gs;
             gs += stride;
+        } else if constexpr (FP) {
+            const auto slot_of = [&](uint32_t it) { return it < nfront ? it : p.count - 1u - (it - nfront); };
+            if (gs < total) {  // the wave's own item, once
+                item = gs;
+                gs = total;
+            } else {
+                if (exhausted >= 8) break;
+                const uint32_t it0 = stride + (uint32_t)x;  // sub-queue x: items it0 + 8 k, k < nx
+                const uint32_t nx = total > it0 ? (total - it0 + 7u) / 8u : 0u;
+                uint32_t k = nx;
+                if (known < nx) {  // (otherwise nothing is left there: no atomic needed to learn it)
+                    if (lane == 0) k = atomicAdd(p.heads + 32 * x, 1u);
+                    k = (uint32_t)__shfl((int)k, 0, 64);
+                }
+                if (k >= nx) {
+                    x = (x + 1) & 7;
+                    ++exhausted;
+                    known = 0;
+                    continue;
+                }
+                known = k + 1u;
+                item = it0 + 8u * k;
+            }
+            cw = p.queue[slot_of(item)];
         } else {
             if (exhausted >= 8) break;
             uint32_t k = 0;
