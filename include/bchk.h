@@ -315,10 +315,28 @@ typedef struct bchk_polar bchk_polar;
  * coset enumeration below 16, the trellis for 16..32 (at most 2^12 states per depth), and an
  * exact ordered-statistics search above 32 (the 64 x 64 extended-BCH kernel; the reference's
  * trellis processor stops below 64) -- the same value bit for bit;
- * 1 <= list_size <= 32, lengths whose per-wave state fits the 160 KiB LDS (U <= 1024 at
- * L = 16, 2048 at L = 8 for all-Arikan codes). Kernel files are read relative to kdir. */
+ * 1 <= list_size <= 32, lengths whose per-wave state fits the 160 KiB LDS (for all-Arikan
+ * codes about 4.4 bytes per symbol and path: U <= 2048 at L = 16, 4096 at L = 8, 8192 at
+ * L = 4; longer ones decode with bchk_polar_create_tiered). Kernel files are read relative to
+ * kdir. */
 int bchk_polar_create(const char *spec, int list_size, int device, bchk_polar **out);
 int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out);
+/* The same decoder for all-Arikan codes up to U = 16384 at any list size: the LLR layers S_l
+ * and partial sums C_l of the layers l <= split (and the codeword C_0) live in a workspace in
+ * device memory, shared between the paths of a list and copied only when written (Tal and
+ * Vardy's lazy copy); the layers below the split stay in LDS. Lists are bit for bit those of
+ * bchk_polar_create_kdir. split = -1: the library chooses -- the smallest split whose LDS part
+ * fits 160 KiB, then further layers out while that lets one more wave onto a CU, up to 8; split in
+ * 1..layers: the boundary exactly there. BCHK_EINVAL before any device call for a matrix or named
+ * layer, a split out of range, U > 16384, or an LDS part above 160 KiB at the split asked for.
+ * The workspace (grid x bytes per workgroup) is allocated here and freed by bchk_polar_destroy;
+ * the grid shrinks to keep it within BCHK_POLAR_WORKSPACE_MB MiB (default 1024). Every other
+ * bchk_polar_* call takes such a context; the genie-aided SC calls keep their own LDS limit. */
+int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
+                             bchk_polar **out);
+/* Where a context keeps its list state (any may be NULL): the split in use (0: all in LDS), LDS
+ * bytes per workgroup, workspace bytes per workgroup (0 unless tiered), workgroups of a launch. */
+int bchk_polar_state_info(const bchk_polar *pc, int *split, uint64_t *lds_bytes, uint64_t *workspace_bytes, int *grid);
 void bchk_polar_destroy(bchk_polar *pc);
 /* N (transmitted length), K, U (unshortened length), L */
 int bchk_polar_params(const bchk_polar *pc, int *n, int *k, int *unshortened, int *list_size);
@@ -346,7 +364,8 @@ int bchk_polar_decode_device(bchk_polar *pc, const float *d_llr, size_t B, uint8
 int bchk_polar_last_launches(const bchk_polar *pc, uint64_t *launches);
 /* Device scratch the context holds for budgeted calls, in bytes: 4 per codeword of the largest
  * batch so far, one save slot of *save_stride bytes (may be NULL; 0 for codes without a search
- * layer) per workgroup of the largest grid so far, and two counter words. */
+ * layer) per workgroup of the largest grid so far, and two counter words; plus a tiered
+ * context's workspace. */
 int bchk_polar_scratch_bytes(const bchk_polar *pc, uint64_t *bytes, uint64_t *save_stride);
 /* CMixedKernelEncoder::Encode (MixedKernelEncoder.cpp:142-177), host side: info [B][K] ->
  * codewords [B][N]. */

@@ -40,7 +40,7 @@ EXPORTS = (
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
     "bchk_polar_scratch_bytes", "bchk_polar_encode_device", "bchk_polar_generate_device",
-    "bchk_polar_count_device", "bchk_polar_sweep_device",
+    "bchk_polar_count_device", "bchk_polar_sweep_device", "bchk_polar_create_tiered", "bchk_polar_state_info",
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
     "bchk_kernel_column_search",
     "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
@@ -122,6 +122,8 @@ def lib():
     L.bchk_first_pass_waves.argtypes = [vp, C.POINTER(C.c_uint32)]
     L.bchk_polar_create.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bchk_polar_create_kdir.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.bchk_polar_create_tiered.argtypes = [C.c_char_p, C.c_char_p, i32, i32, i32, C.POINTER(vp)]
+    L.bchk_polar_state_info.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.bchk_polar_destroy.argtypes = [vp]
     L.bchk_polar_destroy.restype = None
     L.bchk_polar_params.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
@@ -420,12 +422,25 @@ class PolarListDecoder:
     (5 x 5, rows as CA5Kernel::Multiply computes them), in any case, decoded by their own f/g
     processors with the state carried per path: code lengths such as 12, 24, 40, 60, 96. With
     L > 1 the lists are the reference's bit for bit where the reference is defined (every G
-    the innermost layer; A5 anywhere), see include/bchk.h and DESIGN 5.14."""
+    the innermost layer; A5 anywhere), see include/bchk.h and DESIGN 5.14.
 
-    def __init__(self, spec, L, device=0, kernel_dir=None):
+    state="lds" keeps every path's state in LDS, which bounds the length (about U L <= 36000 for
+    all-Arikan codes). state="tiered" (all-Arikan codes, U <= 16384, any L <= 32) moves the layers
+    1..split to a device-memory workspace shared between the paths, with the same
+    lists bit for bit; split=None lets the library choose the boundary."""
+
+    def __init__(self, spec, L, device=0, kernel_dir=None, state="lds", split=None):
+        if state not in ("lds", "tiered"):
+            raise ValueError(f"state must be 'lds' or 'tiered', not {state!r}")
+        if state == "lds" and split is not None:
+            raise ValueError("split applies to state='tiered' only")
         h = C.c_void_p()
-        _check(lib().bchk_polar_create_kdir(spec.encode(), kernel_dir.encode() if kernel_dir else None, L, device,
-                                            C.byref(h)))
+        kdir = kernel_dir.encode() if kernel_dir else None
+        if state == "tiered":
+            _check(lib().bchk_polar_create_tiered(spec.encode(), kdir, L, device, -1 if split is None else int(split),
+                                                  C.byref(h)))
+        else:
+            _check(lib().bchk_polar_create_kdir(spec.encode(), kdir, L, device, C.byref(h)))
         self._h = h
         n, k, u, l = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         _check(lib().bchk_polar_params(h, C.byref(n), C.byref(k), C.byref(u), C.byref(l)))
@@ -449,6 +464,18 @@ class PolarListDecoder:
     @property
     def stream(self):
         return lib().bchk_polar_stream(self._h)
+
+    def state_info(self):
+        """dict(split, lds_bytes, workspace_bytes, grid): the boundary in use (0: all in LDS), LDS and
+        workspace bytes per workgroup (one codeword in flight each), workgroups of a launch."""
+        s, g, l, w = C.c_int(), C.c_int(), C.c_uint64(), C.c_uint64()
+        _check(lib().bchk_polar_state_info(self._h, C.byref(s), C.byref(l), C.byref(w), C.byref(g)))
+        return dict(split=s.value, lds_bytes=l.value, workspace_bytes=w.value, grid=g.value)
+
+    @property
+    def split(self):
+        """The layers 1..split are in the device-memory tier (0: every layer in LDS)."""
+        return self.state_info()["split"]
 
     def encode(self, info):
         info = np.ascontiguousarray(info, np.uint8)
@@ -528,7 +555,8 @@ class PolarListDecoder:
         return n.value
 
     def scratch_bytes(self):
-        """(device scratch held for budgeted calls, bytes of one workgroup's save slot)."""
+        """(device scratch held for budgeted calls and the tiered workspace, bytes of one workgroup's
+        save slot)."""
         b, s = C.c_uint64(), C.c_uint64()
         _check(lib().bchk_polar_scratch_bytes(self._h, C.byref(b), C.byref(s)))
         return b.value, s.value

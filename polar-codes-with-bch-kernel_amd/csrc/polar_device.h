@@ -302,4 +302,48 @@ __host__ __device__ inline PolarListLayout polar_list_layout(int U, int L, int K
     return o;
 }
 
+// ---- the tiered all-Arikan kernel (polar_sclist_tiered.hip): S_λ and C_λ of the layers
+// λ <= split, and C_0, live in a per-workgroup workspace in global memory; the layers below the
+// split stay in LDS in polar_list_layout's form for the sub-code of length U >> split.
+struct PolarTieredParams {
+    PolarParams p;
+    uint8_t *ws;         // [grid][ws_bytes] (PolarTieredLayout)
+    int32_t split;
+    int32_t cwsplit;     // packed words of C_0 .. C_split: cwoff[split + 1], or all of them at split = n
+    int32_t cwall;       // packed words of C_0 .. C_n
+};
+// words of the packed C_λ (polar_cw_layout: U bits at λ = 0, U >> (λ-1) after, whole words)
+constexpr int polar_cw_words(int U, int lam) {
+    return lam == 0 ? ((U + 31) >> 5) : (((U >> (lam - 1)) + 31) >> 5);
+}
+// LDS: per path the S layers split+1 .. n (floats, at 0; layer λ at (U >> split) - (U >> (λ-1)))
+// and their packed C (word cwoff[λ] - cwsplit of the path's pathC words), the global layers'
+// array index of every path (idx[(λ-1) L + q], bytes) and one array-owner byte per array, then
+// act / rec as in PolarListLayout.
+// Workspace of one workgroup: per global layer λ = 1..split L arrays of U >> λ floats, layer λ at
+// float L (U - (U >> (λ-1))); at w_C, L arrays per packed layer, layer λ at word L cwoff[λ]
+// (C_0's arrays belong to the paths, the others are shared through idx).
+struct PolarTieredLayout {
+    int pathS, pathC, n_C;  // LDS strides per path (floats, words) and the C words in use
+    int o_C, o_idx, o_own, o_act;
+    uint32_t bytes;
+    uint64_t w_C, ws_bytes;
+};
+__host__ __device__ inline PolarTieredLayout polar_tiered_layout(int U, int L, int K, int split, int cwsplit,
+                                                                 int cwall) {
+    PolarTieredLayout o;
+    const int Us = U >> split;  // 1 at split = n: nothing of S or C in LDS
+    o.pathS = Us > 1 ? polar_path_s(Us) : 0;
+    o.n_C = cwall - cwsplit;
+    o.pathC = o.n_C ? (o.n_C | 1) : 0;
+    o.o_C = 4 * o.pathS * L;
+    o.o_idx = o.o_C + 4 * o.pathC * L;
+    o.o_own = o.o_idx + split * L;
+    o.o_act = (o.o_own + L + 15) & ~15;
+    o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
+    o.w_C = (4ull * (uint64_t)L * (uint64_t)(U - Us) + 15ull) & ~15ull;
+    o.ws_bytes = (o.w_C + 4ull * (uint64_t)L * (uint64_t)cwsplit + 255ull) & ~255ull;
+    return o;
+}
+
 }  // namespace bchk

@@ -33,6 +33,8 @@ using namespace bchk;
 namespace bchk {
 hipError_t launch_polar(const PolarParams &p, int grid, size_t lds, hipStream_t s);
 const void *polar_kernel_ptr();
+hipError_t launch_polar_tiered(const PolarTieredParams &p, int grid, size_t lds, hipStream_t s);  // polar_sclist_tiered.hip
+const void *polar_tiered_kernel_ptr();
 hipError_t launch_polar_mixed(const PolarMixedParams &p, int grid, size_t lds, hipStream_t s);
 const void *polar_mixed_kernel_ptr();
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
@@ -127,9 +129,27 @@ struct bchk_polar {
     size_t genie_lds = 0;
     int genie_grid = 0;
     PBuf gdec, gu, gsum;  // decision-LLR and u rows when the caller passes none; bchk_polar_genie_run's counters
+    // tiered state (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`
+    bool tiered = false;
+    int split = 0, cwsplit = 0, cwall = 0;
+    PBuf ws;  // [grid] workspaces of PolarTieredLayout::ws_bytes
 };
 
 namespace {
+
+constexpr size_t kPolarLdsMax = 160 * 1024;
+
+// the tiered kernel's LDS and workspace layout at `split` (polar_device.h)
+PolarTieredLayout tiered_layout(const bchk_polar *c, int split) {
+    int32_t off[kPolarMaxLayers + 1];
+    (void)polar_cw_layout(c->U, off);
+    const int words = off[c->n] + 1;  // C_n is one word
+    return polar_tiered_layout(c->U, c->L, c->K, split, split < c->n ? off[split + 1] : words, words);
+}
+// Waves per CU that LDS allows, up to kTieredWaves: past that the decoder is bound by the
+// latency of its global layers, not by the waves in flight.
+constexpr int kTieredWaves = 8;
+int tiered_waves(size_t lds) { return (int)std::min<size_t>(kTieredWaves, kPolarLdsMax / std::max<size_t>(lds, 1)); }
 
 // the mixed kernel's LDS and save-slot layout (polar_device.h)
 PolarMixedLayout mixed_lds(const bchk_polar *c) {
@@ -466,7 +486,23 @@ int bchk_polar_create(const char *spec, int list_size, int device, bchk_polar **
     return bchk_polar_create_kdir(spec, nullptr, list_size, device, out);
 }
 
+// split: 0 = every path's state in LDS (bchk_polar_create_kdir); -1 or 1..n = tiered
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bchk_polar **out);
+
 int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out) {
+    return polar_create(spec, kdir, list_size, device, 0, out);
+}
+
+int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
+                             bchk_polar **out) {
+    if (split == 0 || split < -1) {
+        if (out) *out = nullptr;
+        return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
+    }
+    return polar_create(spec, kdir, list_size, device, split, out);
+}
+
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bchk_polar **out) {
     if (!out || !spec) return pfail(BCHK_EINVAL, "NULL argument");
     *out = nullptr;
     if (list_size < 1 || list_size > kPolarMaxList)
@@ -477,7 +513,25 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     c->L = list_size;
     c->device = device;
     if (int rc = parse_spec(c, spec, kdir)) return rc;
-    if (c->mixed) {
+    if (split) {
+        if (c->mixed) return pfail(BCHK_EINVAL, "tiered state is built for all-Arikan codes (a matrix or named layer)");
+        if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
+        c->tiered = true;
+        if (split < 0) {
+            // the smallest split whose LDS part fits, then further layers out while that lets
+            // one more wave onto a CU (tiered_waves)
+            int s = 1;
+            while (s < c->n && tiered_layout(c, s).bytes > kPolarLdsMax) ++s;
+            while (s < c->n && tiered_waves(tiered_layout(c, s + 1).bytes) > tiered_waves(tiered_layout(c, s).bytes)) ++s;
+            split = s;
+        }
+        c->split = split;
+        int32_t off[kPolarMaxLayers + 1];
+        (void)polar_cw_layout(c->U, off);
+        c->cwall = off[c->n] + 1;
+        c->cwsplit = split < c->n ? off[split + 1] : c->cwall;
+        c->lds = tiered_layout(c, split).bytes;
+    } else if (c->mixed) {
         PolarMixedParams &m = c->mp;
         const int nl = c->n;
         mixed_layout(c, m);
@@ -512,8 +566,12 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     } else {
         c->lds = polar_list_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     }
-    if (c->lds > 160 * 1024)
+    if (c->lds > kPolarLdsMax) {
+        if (c->tiered)
+            return pfail(BCHK_EINVAL, "length %d with list %d at split %d still needs %zu B of LDS (> 160 KiB)", c->U,
+                         list_size, c->split, c->lds);
         return pfail(BCHK_EINVAL, "length %d with list %d needs %zu B of LDS (> 160 KiB)", c->U, list_size, c->lds);
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
         return pfail(BCHK_ENODEV, "no HIP device visible (the SC-list decoder has no CPU fallback)");
@@ -557,14 +615,28 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
         hipMemcpy(c->d_tab, blob.data(), o, hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return pfail(BCHK_EHIP, "device setup failed");
-    const void *fn = c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
+    const void *fn = c->tiered ? polar_tiered_kernel_ptr() : c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
     if (c->lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, c->lds) != hipSuccess || per_cu <= 0) {
         per_cu = 1;
         (void)hipGetLastError();
     }
+    if (c->tiered) per_cu = std::min(per_cu, kTieredWaves);
     c->grid = polar_grid("bchk_polar", c, c->lds, per_cu, prop.multiProcessorCount);
+    if (c->tiered) {
+        // one workspace per workgroup, allocated once; the grid shrinks to keep them within the
+        // bound (BCHK_POLAR_WORKSPACE_MB, default 1024), down to a single workgroup
+        const uint64_t per_wg = tiered_layout(c, c->split).ws_bytes;
+        int mb = 1024;
+        env_int("BCHK_POLAR_WORKSPACE_MB", &mb, 1, 1 << 20);
+        const uint64_t fit = ((uint64_t)mb << 20) / per_wg;
+        if ((uint64_t)c->grid > fit) c->grid = (int)std::max<uint64_t>(fit, 1);
+        if (env_flag("BCHK_POLAR_DEBUG"))
+            fprintf(stderr, "bchk_polar tiered: split=%d workspace=%llu B x grid %d\n", c->split,
+                    (unsigned long long)per_wg, c->grid);
+        if (int rc = c->ws.ensure((size_t)(per_wg * (uint64_t)c->grid))) return rc;
+    }
     // codes with search layers: launches of at most ~50 ms (BCHK_POLAR_BUDGET_MS, 0 = one
     // launch per call), so no launch holds the GPU for seconds
     if (c->mixed && c->mp.any_ml) {
@@ -591,7 +663,7 @@ int bchk_polar_last_launches(const bchk_polar *c, uint64_t *launches) {
 
 int bchk_polar_scratch_bytes(const bchk_polar *c, uint64_t *bytes, uint64_t *save_stride) {
     if (!c || !bytes) return pfail(BCHK_EINVAL, "NULL argument");
-    *bytes = (uint64_t)c->rstate.cap + c->rsave.cap + c->unfinished.cap;
+    *bytes = (uint64_t)c->rstate.cap + c->rsave.cap + c->unfinished.cap + c->ws.cap;
     if (save_stride) *save_stride = (c->mixed && c->mp.any_ml) ? mixed_lds(c).save_bytes : 0;
     return 0;
 }
@@ -690,7 +762,26 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         }
         return 0;
     }
+    if (c->tiered) {  // grid <= the workspaces allocated at create
+        PolarTieredParams t{};
+        t.p = p;
+        t.ws = (uint8_t *)c->ws.p;
+        t.split = c->split;
+        t.cwsplit = c->cwsplit;
+        t.cwall = c->cwall;
+        PHIP_TRY(launch_polar_tiered(t, grid, c->lds, stream ? (hipStream_t)stream : c->stream));
+        return 0;
+    }
     PHIP_TRY(launch_polar(p, grid, c->lds, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
+
+int bchk_polar_state_info(const bchk_polar *c, int *split, uint64_t *lds_bytes, uint64_t *workspace_bytes, int *grid) {
+    if (!c) return pfail(BCHK_EINVAL, "NULL argument");
+    if (split) *split = c->tiered ? c->split : 0;
+    if (lds_bytes) *lds_bytes = c->lds;
+    if (workspace_bytes) *workspace_bytes = c->tiered ? tiered_layout(c, c->split).ws_bytes : 0;
+    if (grid) *grid = c->grid;
     return 0;
 }
 

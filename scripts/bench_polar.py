@@ -10,6 +10,13 @@ the best path, and the oracle (oracle/polar_oracle.c, one host core) on a bounde
 
     python scripts/bench_polar.py --n 10 --K 512 --L 8 --snr 2.0 --batch 65536
 
+--state tiered [--split S] decodes with the tiered state (csrc/polar_sclist_tiered.hip; codes past
+the LDS limit need it); --grids G makes the batch G times the context's persistent grid, so every
+wave decodes the same number of codewords. The line then also carries the split in use, LDS and
+workspace bytes per codeword in flight, the grid and the waves per CU.
+
+    python scripts/bench_polar.py --n 12 --K 2048 --L 32 --state tiered --grids 8
+
 --sim times the whole simulation instead (bchk_polar_sweep_device: words generated, decoded and
 counted on the GPU, one Eb/N0 point cut by words) in words/s of wall time, at (1024, 512) and
 (64, 32) with L = 8, beside the decode-only rate of the same context in the same run (device
@@ -99,6 +106,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--no-cw", action="store_true", help="do not write the codeword rows")
     ap.add_argument("--cpu-seconds", type=float, default=5.0)
+    ap.add_argument("--state", choices=("lds", "tiered"), default="lds")
+    ap.add_argument("--split", type=int, default=None, help="tiered: the boundary (default: the library's choice)")
+    ap.add_argument("--grids", type=int, default=0, help="batch = this many times the persistent grid")
     a = ap.parse_args()
     if a.sim:
         return sim(a)
@@ -108,11 +118,12 @@ def main():
     from polar_lib import PolarOracle, arikan_spec, awgn_llr
 
     spec = arikan_spec(a.n, a.K, dyn=a.dyn, seed=1)
-    o = PolarOracle(spec)
-    d = load().PolarListDecoder(spec, a.L)
-    N, K, L, B = d.N, d.K, d.L, a.batch
+    o = PolarOracle(spec) if a.n <= 12 else None  # the C oracle stops at U = 4096
+    d = load().PolarListDecoder(spec, a.L, state=a.state, split=a.split)
+    si = d.state_info()
+    N, K, L, B = d.N, d.K, d.L, a.grids * si["grid"] if a.grids else a.batch
     rng = np.random.default_rng(1)
-    base = min(B, 1 << 14)
+    base = min(B, max(64, (1 << 24) >> a.n))  # distinct words (host-encoded), tiled over the batch
     info = rng.integers(0, 2, (base, K)).astype(np.uint8)
     llr = awgn_llr(d.encode(info), a.snr, K / N, seed=2)
     reps = (B + base - 1) // base
@@ -149,7 +160,7 @@ def main():
 
     # parity spot check + CPU baseline on a bounded sample (oracle, one core)
     cpu = None
-    if a.cpu_seconds > 0:
+    if a.cpu_seconds > 0 and o is not None:
         t = time.perf_counter()
         done = 0
         want = []
@@ -167,7 +178,8 @@ def main():
     print(json.dumps({
         "metric": "SC-list codewords/s", "value": cps, "unit": "codewords/s",
         "config": {"workload": f"Arikan polar ({N},{K}) dyn={a.dyn}, L={L}, Eb/N0={a.snr} dB",
-                   "batch": B, "write_codewords": not a.no_cw},
+                   "batch": B, "write_codewords": not a.no_cw, "state": a.state},
+        "state": dict(si, waves_per_cu=si["grid"] / torch.cuda.get_device_properties(0).multi_processor_count),
         "ms_per_step": ms, "wall_s": wall, "fer_best_path": fer,
         "roofline": {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": gbs / HBM_PEAK_GBS, "algo_bytes_per_codeword": algo},
