@@ -334,6 +334,19 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
  * bchk_polar_* call takes such a context; the genie-aided SC calls keep their own LDS limit. */
 int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
                              bchk_polar **out);
+/* The tiered state for codes with matrix or named layers (and, through the same kernel,
+ * all-Arikan ones): polar_mixed_tiered.hip. For every layer j < split (layers counted from the
+ * channel side, 1 <= split <= layers) the layer's LLRs S_{j+1}, partial sums C_{j+1}, offset
+ * state and a named layer's carried floats live in a per-workgroup workspace in device memory,
+ * shared between the paths of a list and copied only when written; the codeword C_0 and the
+ * mapped channel LLRs lie there too; the inner layers stay in LDS. Lists are bit for bit those
+ * of bchk_polar_create_kdir. split = -1: the rule of bchk_polar_create_tiered applied to this
+ * layout. BCHK_EINVAL before any device call for a split out of range, an LDS part above
+ * 160 KiB at the split asked for, or a code with an ordered-statistics layer (a matrix kernel
+ * above 32, or BCHK_POLAR_ML lowered), which stays on the LDS state. Workspace, grid bound
+ * (BCHK_POLAR_WORKSPACE_MB) and the other bchk_polar_* calls as for bchk_polar_create_tiered. */
+int bchk_polar_create_tiered_mixed(const char *spec, const char *kdir, int list_size, int device, int split,
+                                   bchk_polar **out);
 /* Where a context keeps its list state (any may be NULL): the split in use (0: all in LDS), LDS
  * bytes per workgroup, workspace bytes per workgroup (0 unless tiered), workgroups of a launch. */
 int bchk_polar_state_info(const bchk_polar *pc, int *split, uint64_t *lds_bytes, uint64_t *workspace_bytes, int *grid);

@@ -40,7 +40,8 @@ EXPORTS = (
     "bchk_polar_destroy", "bchk_polar_params", "bchk_polar_decode_host", "bchk_polar_decode_device",
     "bchk_polar_encode_host", "bchk_polar_sync", "bchk_polar_stream", "bchk_polar_last_launches",
     "bchk_polar_scratch_bytes", "bchk_polar_encode_device", "bchk_polar_generate_device",
-    "bchk_polar_count_device", "bchk_polar_sweep_device", "bchk_polar_create_tiered", "bchk_polar_state_info",
+    "bchk_polar_count_device", "bchk_polar_sweep_device", "bchk_polar_create_tiered", "bchk_polar_create_tiered_mixed",
+    "bchk_polar_state_info",
     "bchk_kernel_ebch", "bchk_kernel_field_order", "bchk_kernel_trellis_cost", "bchk_kernel_column_costs",
     "bchk_kernel_column_search",
     "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
@@ -123,6 +124,7 @@ def lib():
     L.bchk_polar_create.argtypes = [C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bchk_polar_create_kdir.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
     L.bchk_polar_create_tiered.argtypes = [C.c_char_p, C.c_char_p, i32, i32, i32, C.POINTER(vp)]
+    L.bchk_polar_create_tiered_mixed.argtypes = [C.c_char_p, C.c_char_p, i32, i32, i32, C.POINTER(vp)]
     L.bchk_polar_state_info.argtypes = [vp, C.POINTER(i32), C.POINTER(u64), C.POINTER(u64), C.POINTER(i32)]
     L.bchk_polar_destroy.argtypes = [vp]
     L.bchk_polar_destroy.restype = None
@@ -427,18 +429,22 @@ class PolarListDecoder:
     state="lds" keeps every path's state in LDS, which bounds the length (about U L <= 36000 for
     all-Arikan codes). state="tiered" (all-Arikan codes, U <= 16384, any L <= 32) moves the layers
     1..split to a device-memory workspace shared between the paths, with the same
-    lists bit for bit; split=None lets the library choose the boundary."""
+    lists bit for bit; split=None lets the library choose the boundary. state="tiered_mixed" is
+    that state for codes with matrix or named layers (and all-Arikan ones, through the same
+    kernel, csrc/polar_mixed_tiered.hip): the state of the layers before `split`, counted from the
+    channel side, lives in the workspace; codes with an ordered-statistics layer
+    stay on state="lds"."""
 
     def __init__(self, spec, L, device=0, kernel_dir=None, state="lds", split=None):
-        if state not in ("lds", "tiered"):
-            raise ValueError(f"state must be 'lds' or 'tiered', not {state!r}")
+        if state not in ("lds", "tiered", "tiered_mixed"):
+            raise ValueError(f"state must be 'lds', 'tiered' or 'tiered_mixed', not {state!r}")
         if state == "lds" and split is not None:
-            raise ValueError("split applies to state='tiered' only")
+            raise ValueError("split applies to the tiered states only")
         h = C.c_void_p()
         kdir = kernel_dir.encode() if kernel_dir else None
-        if state == "tiered":
-            _check(lib().bchk_polar_create_tiered(spec.encode(), kdir, L, device, -1 if split is None else int(split),
-                                                  C.byref(h)))
+        if state != "lds":
+            create = lib().bchk_polar_create_tiered if state == "tiered" else lib().bchk_polar_create_tiered_mixed
+            _check(create(spec.encode(), kdir, L, device, -1 if split is None else int(split), C.byref(h)))
         else:
             _check(lib().bchk_polar_create_kdir(spec.encode(), kdir, L, device, C.byref(h)))
         self._h = h

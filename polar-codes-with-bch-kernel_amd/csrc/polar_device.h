@@ -346,4 +346,56 @@ __host__ __device__ inline PolarTieredLayout polar_tiered_layout(int U, int L, i
     return o;
 }
 
+// ---- the tiered mixed-kernel decoder (polar_mixed_tiered.hip): polar_mixed_kernel with the
+// state of the layers j < split of every path in a per-workgroup workspace in global memory.
+// Layer j's group is what its LLR step and the partial sums of its blocks write: S_{j+1}, the
+// named layer's floats F_j, C_{j+1} and the offset state O_j. Per group there are L arrays,
+// shared between the paths through an index table in LDS (Tal and Vardy's lazy copy, as in the
+// tiered all-Arikan kernel); C_0 (one array per path) and the mapped channel LLRs lie there too.
+// The layers j >= split keep the mixed layout for the inner sub-code in LDS.
+// In `m` the per-layer offsets mean, for a global layer j < split, places in one array of its
+// group: S_{j+1} at 0, F_j at float foff[j], C_{j+1} at byte coff[j + 1], O_j at byte ooff[j];
+// for j >= split, places in the path's LDS strides ssize / csize / osize as in PolarMixedParams
+// (soff[j + 1] and foff[j] floats, coff[j + 1] and ooff[j] bytes). Search layers (ml) are not taken.
+struct PolarMixedTieredParams {
+    PolarMixedParams m;
+    uint8_t *ws;                        // [grid][ws_bytes] (PolarMixedTieredLayout)
+    int32_t split;
+    int32_t garr[kPolarMaxLayers];      // bytes of one array of group j
+    int32_t gbase[kPolarMaxLayers];     // first array of group j, bytes past w_grp (L arrays each)
+    int32_t gobytes[kPolarMaxLayers];   // bytes of O_j, and
+    int32_t gfloats[kPolarMaxLayers];   // floats of F_j, in an array of group j
+    int32_t grp_bytes;                  // all groups' arrays: the sum of L garr[j], j < split
+};
+// LDS: per path S / C / O of the inner layers, the groups' array index of every path
+// (idx[j L + q], bytes) and one array-owner byte per array, then phases, kernel rows, act / rec
+// and the trellis metric buffers as in PolarMixedLayout.
+// Workspace of one workgroup: the channel LLRs after LoadLLRs (U floats), C_0 of every path (L
+// arrays of c0 bytes), then the groups' arrays.
+struct PolarMixedTieredLayout {
+    int o_C, o_O, o_idx, o_own, o_ph, o_rows, o_act, o_tm;  // (S at 0)
+    uint32_t bytes;
+    uint32_t c0, w_C0, w_grp;
+    uint64_t ws_bytes;
+};
+__host__ __device__ inline PolarMixedTieredLayout polar_mixed_tiered_layout(int U, int L, int K, int ssize, int csize,
+                                                                            int osize, int nl, int split, int tstates,
+                                                                            int grp_bytes) {
+    PolarMixedTieredLayout o;
+    o.o_C = 4 * ssize * L;
+    o.o_O = o.o_C + csize * L;
+    o.o_idx = o.o_O + osize * L;
+    o.o_own = o.o_idx + split * L;
+    o.o_ph = (o.o_own + L + 15) & ~15;
+    o.o_rows = (o.o_ph + 2 * U + 15) & ~15;
+    o.o_act = o.o_rows + 8 * kPolarMaxKernel * nl;
+    o.o_tm = (o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15;
+    o.bytes = (uint32_t)((o.o_tm + 8 * tstates + 15) & ~15);
+    o.c0 = ((uint32_t)U + 15u) & ~15u;
+    o.w_C0 = (4u * (uint32_t)U + 15u) & ~15u;
+    o.w_grp = o.w_C0 + (uint32_t)L * o.c0;
+    o.ws_bytes = ((uint64_t)o.w_grp + (uint64_t)grp_bytes + 255ull) & ~255ull;
+    return o;
+}
+
 }  // namespace bchk

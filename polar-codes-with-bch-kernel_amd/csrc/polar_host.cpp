@@ -37,6 +37,8 @@ hipError_t launch_polar_tiered(const PolarTieredParams &p, int grid, size_t lds,
 const void *polar_tiered_kernel_ptr();
 hipError_t launch_polar_mixed(const PolarMixedParams &p, int grid, size_t lds, hipStream_t s);
 const void *polar_mixed_kernel_ptr();
+hipError_t launch_polar_mixed_tiered(const PolarMixedTieredParams &p, int grid, size_t lds, hipStream_t s);  // polar_mixed_tiered.hip
+const void *polar_mixed_tiered_kernel_ptr();
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
 hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s);
 hipError_t launch_polar_genie(const PolarGenieParams &p, int grid, size_t lds, hipStream_t s);  // polar_genie.hip
@@ -132,7 +134,11 @@ struct bchk_polar {
     // tiered state (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`
     bool tiered = false;
     int split = 0, cwsplit = 0, cwall = 0;
-    PBuf ws;  // [grid] workspaces of PolarTieredLayout::ws_bytes
+    PBuf ws;  // [grid] workspaces of PolarTieredLayout::ws_bytes (tmixed: PolarMixedTieredLayout's)
+    // tiered mixed-kernel state (polar_mixed_tiered.hip): the groups of the layers j < split in
+    // `ws`; tm.m holds the tiered layout, mp stays the LDS layout (the genie calls use it)
+    bool tmixed = false;
+    PolarMixedTieredParams tm{};
 };
 
 namespace {
@@ -468,6 +474,96 @@ void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
     m.osize = (oo + 15) & ~15;
 }
 
+
+// The mixed layout of a context and how each matrix layer takes its LLRs, with the trellises
+// (c->mp, c->tent / tbase / tlog).
+int mixed_tables(bchk_polar *c) {
+    PolarMixedParams &m = c->mp;
+    const int nl = c->n;
+    mixed_layout(c, m);
+    // matrix layers from the trellis threshold up take their LLRs from the trellis; those
+    // larger than the trellis limit (or from BCHK_POLAR_ML up) from the exact
+    // ordered-statistics search
+    int tmin = 16, mlmin = kPolarMaxTrellisKernel + 1;
+    env_int("BCHK_POLAR_TRELLIS", &tmin, 2, INT_MAX);
+    env_int("BCHK_POLAR_ML", &mlmin, 2, INT_MAX);
+    // the search's round guard (a finite tree: never reached in practice; tests lower it)
+    int rounds = 0;
+    m.ml_rounds = env_int("BCHK_POLAR_ML_ROUNDS", &rounds, 1, INT_MAX) ? (uint32_t)rounds : kMlRoundsDefault;
+    m.any_ml = 0;
+    m.tstates = 0;
+    c->tbase.assign((size_t)nl * kPolarMaxKernel, 0u);
+    c->tlog.assign((size_t)nl * kPolarMaxKernel * (kPolarMaxKernel + 1), 0u);
+    c->tent.clear();
+    for (int j = 0; j < nl; ++j) {
+        const bool matrix = !c->arikan[j] && !c->named[j];  // LLRs over the coset of its rows
+        m.ml[j] = (matrix && c->ksize[j] >= std::min(mlmin, kPolarMaxTrellisKernel + 1)) ? 1 : 0;
+        m.any_ml |= m.ml[j];
+        m.trellis[j] = (matrix && !m.ml[j] && c->ksize[j] >= tmin) ? 1 : 0;
+        if (!m.trellis[j]) continue;
+        const int most = build_trellis(&c->krows[(size_t)j * kPolarMaxKernel], c->ksize[j], c->tent,
+                                       &c->tbase[(size_t)j * kPolarMaxKernel],
+                                       &c->tlog[(size_t)j * kPolarMaxKernel * (kPolarMaxKernel + 1)]);
+        if (!most) return BCHK_EINVAL;  // build_trellis set the message
+        m.tstates = std::max(m.tstates, std::max(64, most));
+    }
+    if (c->tent.empty()) c->tent.push_back(0u);
+    return 0;
+}
+
+// The tiered mixed layout at `split` (polar_device.h PolarMixedTieredParams): the LDS strides
+// and offsets of the inner layers j >= split in mixed_layout's form, and for j < split the parts
+// of one array of the layer's group (S, F, then C and O on 16 bytes).
+void mixed_tiered_layout(const bchk_polar *c, int split, PolarMixedTieredParams &t) {
+    PolarMixedParams &m = t.m;
+    m = c->mp;
+    const int nl = c->n;
+    t.split = split;
+    int grp = 0;
+    for (int j = 0; j < split; ++j) {
+        const int d = m.outer[j + 1], l = c->ksize[j];
+        const bool matrix = !c->arikan[j] && !c->named[j];
+        t.gfloats[j] = polar_named_floats(c->named[j]) * d;
+        t.gobytes[j] = matrix ? l * d : (c->named[j] == kNamedA5 ? d : 0);
+        m.soff[j + 1] = 0;
+        m.foff[j] = d;
+        m.coff[j + 1] = (4 * (d + t.gfloats[j]) + 15) & ~15;
+        m.ooff[j] = (m.coff[j + 1] + l * d + 15) & ~15;
+        t.garr[j] = (m.ooff[j] + t.gobytes[j] + 15) & ~15;
+        t.gbase[j] = grp;
+        grp += c->L * t.garr[j];
+    }
+    t.grp_bytes = grp;
+    m.coff[0] = 0;
+    int so = 0, co = 0, oo = 0;
+    for (int lam = split + 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
+    for (int lam = split + 1; lam <= nl; ++lam) { m.coff[lam] = co; co += m.outer[lam] * c->ksize[lam - 1]; }
+    bool any_named = false;
+    for (int j = split; j < nl; ++j) {
+        m.ooff[j] = oo;
+        m.foff[j] = so;
+        if (c->named[j]) {
+            any_named = true;
+            so += polar_named_floats(c->named[j]) * m.outer[j + 1];
+            if (c->named[j] == kNamedA5) oo += m.outer[j + 1];
+        } else if (!c->arikan[j]) {
+            oo += c->ksize[j] * m.outer[j + 1];
+        }
+    }
+    m.ssize = so ? ((so + 3) & ~3) + (any_named ? 4 : 0) : 0;
+    m.csize = (co + 15) & ~15;
+    m.osize = (oo + 15) & ~15;
+}
+PolarMixedTieredLayout mixed_tiered_lds(const bchk_polar *c, const PolarMixedTieredParams &t) {
+    const PolarMixedParams &m = t.m;
+    return polar_mixed_tiered_layout(c->U, c->L, c->K, m.ssize, m.csize, m.osize, m.nl, t.split, m.tstates, t.grp_bytes);
+}
+size_t mixed_tiered_lds_at(const bchk_polar *c, int split) {
+    PolarMixedTieredParams t{};
+    mixed_tiered_layout(c, split, t);
+    return mixed_tiered_lds(c, t).bytes;
+}
+
 }  // namespace
 
 extern "C" {
@@ -486,11 +582,22 @@ int bchk_polar_create(const char *spec, int list_size, int device, bchk_polar **
     return bchk_polar_create_kdir(spec, nullptr, list_size, device, out);
 }
 
-// split: 0 = every path's state in LDS (bchk_polar_create_kdir); -1 or 1..n = tiered
-static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bchk_polar **out);
+// split: 0 = every path's state in LDS (bchk_polar_create_kdir); -1 or 1..n = tiered, through
+// the all-Arikan kernel or (tmixed) the mixed-kernel one
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bool tmixed,
+                        bchk_polar **out);
 
 int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out) {
-    return polar_create(spec, kdir, list_size, device, 0, out);
+    return polar_create(spec, kdir, list_size, device, 0, false, out);
+}
+
+int bchk_polar_create_tiered_mixed(const char *spec, const char *kdir, int list_size, int device, int split,
+                                   bchk_polar **out) {
+    if (split == 0 || split < -1) {
+        if (out) *out = nullptr;
+        return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
+    }
+    return polar_create(spec, kdir, list_size, device, split, true, out);
 }
 
 int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
@@ -499,10 +606,11 @@ int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, 
         if (out) *out = nullptr;
         return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
     }
-    return polar_create(spec, kdir, list_size, device, split, out);
+    return polar_create(spec, kdir, list_size, device, split, false, out);
 }
 
-static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bchk_polar **out) {
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bool tmixed,
+                        bchk_polar **out) {
     if (!out || !spec) return pfail(BCHK_EINVAL, "NULL argument");
     *out = nullptr;
     if (list_size < 1 || list_size > kPolarMaxList)
@@ -513,7 +621,24 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
     c->L = list_size;
     c->device = device;
     if (int rc = parse_spec(c, spec, kdir)) return rc;
-    if (split) {
+    if (split && tmixed) {
+        if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
+        if (int rc = mixed_tables(c)) return rc;
+        if (c->mp.any_ml)
+            return pfail(BCHK_EINVAL, "the tiered mixed state does not take a code with a search layer (a matrix kernel "
+                                      "above %d, or BCHK_POLAR_ML): its save slots cover the LDS state", kPolarMaxTrellisKernel);
+        c->tmixed = true;
+        if (split < 0) {
+            // the rule of the all-Arikan tiered state on this layout, counting layers
+            int s = 1;
+            while (s < c->n && mixed_tiered_lds_at(c, s) > kPolarLdsMax) ++s;
+            while (s < c->n && tiered_waves(mixed_tiered_lds_at(c, s + 1)) > tiered_waves(mixed_tiered_lds_at(c, s))) ++s;
+            split = s;
+        }
+        c->split = split;
+        mixed_tiered_layout(c, split, c->tm);
+        c->lds = mixed_tiered_lds(c, c->tm).bytes;
+    } else if (split) {
         if (c->mixed) return pfail(BCHK_EINVAL, "tiered state is built for all-Arikan codes (a matrix or named layer)");
         if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
         c->tiered = true;
@@ -532,42 +657,13 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         c->cwsplit = split < c->n ? off[split + 1] : c->cwall;
         c->lds = tiered_layout(c, split).bytes;
     } else if (c->mixed) {
-        PolarMixedParams &m = c->mp;
-        const int nl = c->n;
-        mixed_layout(c, m);
-        // matrix layers from the trellis threshold up take their LLRs from the trellis; those
-        // larger than the trellis limit (or from BCHK_POLAR_ML up) from the exact
-        // ordered-statistics search
-        int tmin = 16, mlmin = kPolarMaxTrellisKernel + 1;
-        env_int("BCHK_POLAR_TRELLIS", &tmin, 2, INT_MAX);
-        env_int("BCHK_POLAR_ML", &mlmin, 2, INT_MAX);
-        // the search's round guard (a finite tree: never reached in practice; tests lower it)
-        int rounds = 0;
-        m.ml_rounds = env_int("BCHK_POLAR_ML_ROUNDS", &rounds, 1, INT_MAX) ? (uint32_t)rounds : kMlRoundsDefault;
-        m.any_ml = 0;
-        m.tstates = 0;
-        c->tbase.assign((size_t)nl * kPolarMaxKernel, 0u);
-        c->tlog.assign((size_t)nl * kPolarMaxKernel * (kPolarMaxKernel + 1), 0u);
-        c->tent.clear();
-        for (int j = 0; j < nl; ++j) {
-            const bool matrix = !c->arikan[j] && !c->named[j];  // LLRs over the coset of its rows
-            m.ml[j] = (matrix && c->ksize[j] >= std::min(mlmin, kPolarMaxTrellisKernel + 1)) ? 1 : 0;
-            m.any_ml |= m.ml[j];
-            m.trellis[j] = (matrix && !m.ml[j] && c->ksize[j] >= tmin) ? 1 : 0;
-            if (!m.trellis[j]) continue;
-            const int most = build_trellis(&c->krows[(size_t)j * kPolarMaxKernel], c->ksize[j], c->tent,
-                                           &c->tbase[(size_t)j * kPolarMaxKernel],
-                                           &c->tlog[(size_t)j * kPolarMaxKernel * (kPolarMaxKernel + 1)]);
-            if (!most) return BCHK_EINVAL;  // build_trellis set the message
-            m.tstates = std::max(m.tstates, std::max(64, most));
-        }
-        if (c->tent.empty()) c->tent.push_back(0u);
+        if (int rc = mixed_tables(c)) return rc;
         c->lds = mixed_lds(c).bytes;
     } else {
         c->lds = polar_list_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     }
     if (c->lds > kPolarLdsMax) {
-        if (c->tiered)
+        if (c->tiered || c->tmixed)
             return pfail(BCHK_EINVAL, "length %d with list %d at split %d still needs %zu B of LDS (> 160 KiB)", c->U,
                          list_size, c->split, c->lds);
         return pfail(BCHK_EINVAL, "length %d with list %d needs %zu B of LDS (> 160 KiB)", c->U, list_size, c->lds);
@@ -615,19 +711,19 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         hipMemcpy(c->d_tab, blob.data(), o, hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return pfail(BCHK_EHIP, "device setup failed");
-    const void *fn = c->tiered ? polar_tiered_kernel_ptr() : c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
+    const void *fn = c->tmixed ? polar_mixed_tiered_kernel_ptr() : c->tiered ? polar_tiered_kernel_ptr() : c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
     if (c->lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, c->lds) != hipSuccess || per_cu <= 0) {
         per_cu = 1;
         (void)hipGetLastError();
     }
-    if (c->tiered) per_cu = std::min(per_cu, kTieredWaves);
+    if (c->tiered || c->tmixed) per_cu = std::min(per_cu, kTieredWaves);
     c->grid = polar_grid("bchk_polar", c, c->lds, per_cu, prop.multiProcessorCount);
-    if (c->tiered) {
+    if (c->tiered || c->tmixed) {
         // one workspace per workgroup, allocated once; the grid shrinks to keep them within the
         // bound (BCHK_POLAR_WORKSPACE_MB, default 1024), down to a single workgroup
-        const uint64_t per_wg = tiered_layout(c, c->split).ws_bytes;
+        const uint64_t per_wg = c->tmixed ? mixed_tiered_lds(c, c->tm).ws_bytes : tiered_layout(c, c->split).ws_bytes;
         int mb = 1024;
         env_int("BCHK_POLAR_WORKSPACE_MB", &mb, 1, 1 << 20);
         const uint64_t fit = ((uint64_t)mb << 20) / per_wg;
@@ -639,7 +735,7 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
     }
     // codes with search layers: launches of at most ~50 ms (BCHK_POLAR_BUDGET_MS, 0 = one
     // launch per call), so no launch holds the GPU for seconds
-    if (c->mixed && c->mp.any_ml) {
+    if (c->mixed && c->mp.any_ml && !c->tmixed) {
         double ms = 50.0;
         env_double("BCHK_POLAR_BUDGET_MS", &ms, 0.0, DBL_MAX);
         c->budget_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
@@ -700,8 +796,10 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
     p.K = c->K;
     p.L = c->L;
     const int grid = (int)std::min<size_t>((size_t)c->grid, B);
-    if (c->mixed) {
-        PolarMixedParams m = c->mp;
+    if (c->mixed || c->tmixed) {
+        PolarMixedTieredParams t = c->tm;  // (tmixed; grid <= the workspaces allocated at create)
+        PolarMixedParams &m = t.m;
+        if (!c->tmixed) m = c->mp;
         m.llr = p.llr;
         m.info = p.info;
         m.cw = p.cw;
@@ -721,6 +819,11 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         m.K = c->K;
         m.L = c->L;
         hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+        if (c->tmixed) {
+            t.ws = (uint8_t *)c->ws.p;
+            PHIP_TRY(launch_polar_mixed_tiered(t, grid, c->lds, s));
+            return 0;
+        }
         if (!(m.any_ml && c->budget_ticks)) {
             PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
             return 0;
@@ -778,9 +881,10 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
 
 int bchk_polar_state_info(const bchk_polar *c, int *split, uint64_t *lds_bytes, uint64_t *workspace_bytes, int *grid) {
     if (!c) return pfail(BCHK_EINVAL, "NULL argument");
-    if (split) *split = c->tiered ? c->split : 0;
+    if (split) *split = (c->tiered || c->tmixed) ? c->split : 0;
     if (lds_bytes) *lds_bytes = c->lds;
-    if (workspace_bytes) *workspace_bytes = c->tiered ? tiered_layout(c, c->split).ws_bytes : 0;
+    if (workspace_bytes)
+        *workspace_bytes = c->tmixed ? mixed_tiered_lds(c, c->tm).ws_bytes : c->tiered ? tiered_layout(c, c->split).ws_bytes : 0;
     if (grid) *grid = c->grid;
     return 0;
 }

@@ -1,5 +1,5 @@
 // polar_llr_device.h -- the per-layer LLR and partial-sum routines of SC decoding over mixed
-// kernels, shared by the SC-list kernel (polar_mixed.hip) and the genie-aided single-path
+// kernels, shared by the SC-list kernels (polar_mixed.hip, polar_mixed_tiered.hip) and the genie-aided single-path
 // kernel (polar_genie.hip): one copy of the arithmetic, so both give the same bits.
 //
 // Arikan layers: the f/g of SoftProcessing.cpp:39-80. Matrix layers:
@@ -295,6 +295,27 @@ __device__ __forceinline__ void update_c(const uint64_t *rows, const int32_t *ks
         stride = next;
         ph2 = psi;
         --lam;
+    }
+}
+
+// One layer of update_c's loop, its arithmetic restated, for a caller whose C_λ and C_{λ-1} lie
+// in different memories (polar_mixed_tiered.hip; update_c itself stays as it is, so the kernels
+// that call it compile as before): the finished block of C_λ (Xof(q): l inputs of `stride`
+// elements each; kr the kernel's rows) times the kernel, into Yof(q) = C_{λ-1} from byte phi0 on.
+// No synchronisation.
+template <class PathOf, class XOf, class YOf>
+__device__ __forceinline__ void update_c_layer(const uint64_t *kr, int l, int stride, int phi0, int nact, int lane,
+                                               PathOf pathof, XOf Xof, YOf Yof) {
+    const int tot = nact * stride;
+    for (int it = lane; it < tot; it += 64) {
+        const int q = pathof(it / stride), s = it % stride;
+        const uint8_t *x = Xof(q);
+        uint8_t *yo = Yof(q) + phi0;
+        // (y_i) = (x_j) K: y_i = XOR over rows j with K[j][i] (LinAlg.cpp:685-709)
+        uint64_t yv = 0;
+        for (int jj = 0; jj < l; ++jj)
+            if (x[jj * stride + s] & 1u) yv ^= kr[jj];
+        for (int i = 0; i < l; ++i) yo[i * stride + s] = (uint8_t)((yv >> i) & 1ull);
     }
 }
 
