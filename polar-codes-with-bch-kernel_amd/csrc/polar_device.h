@@ -1,8 +1,12 @@
 // polar_device.h -- what the host runtime (polar_host.cpp) shares with the gfx950 polar
 // kernels: the parameter blocks, LDS layouts and save-slot format of the SC-list decoders
 // (polar_sclist.hip, polar_mixed.hip), the simulation front-end (polar_channel.hip) and
-// genie-aided SC (polar_genie.hip). Plain C++, no HIP types.
+// genie-aided SC (polar_genie.hip). PolarIo opens both decoder parameter blocks. The device
+// routines the kernels share are in polar_list_device.h (decisions, LoadLLRs),
+// polar_llr_device.h (SoftXOR, mixed-kernel LLRs and partial sums) and polar_tier_device.h (the
+// tiered kernels' index table). Plain C++, no HIP types.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace bchk {
@@ -10,8 +14,10 @@ namespace bchk {
 constexpr int kPolarMaxList = 32;    // 2 L candidates, one per lane of a wave
 constexpr int kPolarMaxLayers = 14;  // U <= 2^14 (LDS bounds it further)
 
-// One SC-list decode launch: B codewords, one wave each, every path's arrays in LDS.
-struct PolarParams {
+// The caller's buffers and the code's tables that every SC-list kernel reads and writes: the
+// first member of both parameter blocks, filled once by the host (polar_host.cpp) and used by
+// the kernels' LoadLLRs (plist::chan_llr) and epilogues.
+struct PolarIo {
     const float *llr;       // [B][N] channel LLRs, log P(0)/P(1) (the decoder's reading)
     uint8_t *info;          // [B][L][K] information vectors, best path first
     uint8_t *cw;            // [B][L][N] codewords (may be null)
@@ -21,11 +27,18 @@ struct PolarParams {
     const uint16_t *phase;  // [U] bit 0 frozen | (dynamic-freezing bit + 1) << 1 | has-correction << 8
     const uint64_t *dfcorr; // [U] dynamic-freezing correction masks
     const int16_t *cwpos;   // [N] transmitted (neither shortened nor punctured) symbols
+};
+
+// One SC-list decode launch: B codewords, one wave each, every path's arrays in LDS.
+struct PolarParams {
+    PolarIo io;
     uint32_t B;
     int32_t n, U, N, K, L;
     int32_t pathCw;                       // packed partial-sum words per path
     int32_t cwoff[kPolarMaxLayers + 1];   // word offset of C_λ in a path's packed array
 };
+// the kernel arguments keep their byte layout
+static_assert(sizeof(PolarIo) == 72 && offsetof(PolarParams, B) == 72 && sizeof(PolarParams) == 160, "PolarParams layout");
 
 constexpr uint16_t kPhaseFrozen = 1u, kPhaseCorr = 0x100u;
 
@@ -84,14 +97,7 @@ constexpr uint32_t kTrellisZ = 1u << 13, kTrellisValid = 1u << 14, kTrellisState
 constexpr uint8_t kNamedG = 1, kNamedA5 = 2;
 constexpr int polar_named_floats(int kind) { return kind == kNamedG ? 1 : kind == kNamedA5 ? 3 : 0; }
 struct PolarMixedParams {
-    const float *llr;
-    uint8_t *info, *cw;
-    float *metric;
-    int32_t *count;
-    const int16_t *symmap;
-    const uint16_t *phase;
-    const uint64_t *dfcorr;
-    const int16_t *cwpos;
+    PolarIo io;
     const uint64_t *krows;  // [nl][kPolarMaxKernel]
     const uint32_t *tent, *tbase;  // trellis predecessor lists (see above)
     const uint8_t *tlog;
@@ -128,6 +134,7 @@ struct PolarMixedParams {
     uint32_t ml_rounds;     // a search past this many rounds in all gives NaN (BCHK_POLAR_ML_ROUNDS)
 };
 constexpr uint32_t kMlRoundsDefault = 1u << 20;
+static_assert(offsetof(PolarMixedParams, krows) == 72 && sizeof(PolarMixedParams) == 608, "PolarMixedParams layout");
 
 // A suspended codeword's save slot (PolarMixedParams::rsave): the header, six registers per
 // lane, then the LDS of the list state -- channel / S / C / O ([0, o_ph)) at kSaveLdsOff,

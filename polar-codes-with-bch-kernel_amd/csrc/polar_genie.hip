@@ -63,10 +63,7 @@ __global__ void __launch_bounds__(64) polar_genie_kernel(PolarGenieParams p) {
         uint8_t *urow = p.u + (size_t)cw * U;
         for (int i = lane; i < U; i += 64) urow[i] = (uint8_t)penc::ubit(u32, i);
         const float *y = p.llr + (size_t)cw * t.N;  // LoadLLRs (MixedKernelEncoder.cpp:181-207)
-        for (int i = lane; i < U; i += 64) {
-            const int m = p.symmap[i];
-            chan[i] = m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
-        }
+        for (int i = lane; i < U; i += 64) chan[i] = plist::chan_llr(p.symmap, y, i);
         wsync();
         float *drow = p.dec_llr + (size_t)cw * U;
         float keep = 0.0f;  // LLR of phase (phi & ~63) + lane

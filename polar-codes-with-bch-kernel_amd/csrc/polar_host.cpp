@@ -91,6 +91,7 @@ struct PBuf {
 }  // namespace
 
 struct bchk_polar {
+    enum class PolarState { List, Mixed, ListTiered, MixedTiered };
     int N = 0, K = 0, U = 0, n = 0, L = 0, device = 0;
     // layers: kernel size, Arikan flag, rows as bitmasks (bit c = K[r][c]); mixed = any
     // matrix or named (G / A5) layer (decoded by polar_mixed_kernel)
@@ -131,15 +132,17 @@ struct bchk_polar {
     size_t genie_lds = 0;
     int genie_grid = 0;
     PBuf gdec, gu, gsum;  // decision-LLR and u rows when the caller passes none; bchk_polar_genie_run's counters
-    // tiered state (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`
-    bool tiered = false;
+    // Where the path state lives, and so which kernel decodes. ListTiered
+    // (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`. MixedTiered
+    // (polar_mixed_tiered.hip): the groups of the layers j < split in `ws`; tm.m holds the tiered
+    // layout, mp stays the LDS layout (the genie calls use it).
+    PolarState state = PolarState::List;
     int split = 0, cwsplit = 0, cwall = 0;
-    PBuf ws;  // [grid] workspaces of PolarTieredLayout::ws_bytes (tmixed: PolarMixedTieredLayout's)
-    // tiered mixed-kernel state (polar_mixed_tiered.hip): the groups of the layers j < split in
-    // `ws`; tm.m holds the tiered layout, mp stays the LDS layout (the genie calls use it)
-    bool tmixed = false;
+    PBuf ws;  // [grid] workspaces of ws_bytes(c) each
     PolarMixedTieredParams tm{};
+    bool is_tiered() const { return state == PolarState::ListTiered || state == PolarState::MixedTiered; }
 };
+using State = bchk_polar::PolarState;
 
 namespace {
 
@@ -443,21 +446,15 @@ int parse_spec(bchk_polar *c, const char *spec, const char *kdir) {
 // S stride and A5's bit takes the layer's place in the offset-state stride (polar_device.h).
 // With such a layer the S stride gets polar_path_s's 16 bytes of padding: the state is read
 // and written at stride d across the lanes, like S, one path after the other.
-void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
+// The strides and offsets of the layers from `first` on (S_{first+1} .. and C_{first+1} ..,
+// counted from 0) are what both layouts share.
+void inner_layout(const bchk_polar *c, int first, PolarMixedParams &m) {
     const int nl = c->n;
-    m.nl = nl;
-    m.outer[0] = c->U;
-    for (int j = 0; j < nl; ++j) {
-        m.ksize[j] = c->ksize[j];
-        m.arikan[j] = c->arikan[j];
-        m.named[j] = c->named[j];
-        m.outer[j + 1] = m.outer[j] / c->ksize[j];
-    }
-    int so = 0, co = 0, oo = 0;
-    for (int lam = 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
-    for (int lam = 0; lam <= nl; ++lam) { m.coff[lam] = co; co += lam ? m.outer[lam] * c->ksize[lam - 1] : m.outer[0]; }
+    int so = 0, co = first ? 0 : m.outer[0], oo = 0;  // C_0 leads the path's C stride when it is in LDS
+    for (int lam = first + 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
+    for (int lam = first + 1; lam <= nl; ++lam) { m.coff[lam] = co; co += m.outer[lam] * c->ksize[lam - 1]; }
     bool any_named = false;
-    for (int j = 0; j < nl; ++j) {
+    for (int j = first; j < nl; ++j) {
         m.ooff[j] = oo;
         m.foff[j] = so;
         if (c->named[j]) {
@@ -468,12 +465,24 @@ void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
             oo += c->ksize[j] * m.outer[j + 1];
         }
     }
-    m.soff[0] = 0;
-    m.ssize = ((so + 3) & ~3) + (any_named ? 4 : 0);
+    m.ssize = (so || !first) ? ((so + 3) & ~3) + (any_named ? 4 : 0) : 0;
     m.csize = (co + 15) & ~15;
     m.osize = (oo + 15) & ~15;
 }
-
+void mixed_layout(const bchk_polar *c, PolarMixedParams &m) {
+    const int nl = c->n;
+    m.nl = nl;
+    m.outer[0] = c->U;
+    for (int j = 0; j < nl; ++j) {
+        m.ksize[j] = c->ksize[j];
+        m.arikan[j] = c->arikan[j];
+        m.named[j] = c->named[j];
+        m.outer[j + 1] = m.outer[j] / c->ksize[j];
+    }
+    m.soff[0] = 0;
+    m.coff[0] = 0;
+    inner_layout(c, 0, m);
+}
 
 // The mixed layout of a context and how each matrix layer takes its LLRs, with the trellises
 // (c->mp, c->tent / tbase / tlog).
@@ -517,7 +526,6 @@ int mixed_tables(bchk_polar *c) {
 void mixed_tiered_layout(const bchk_polar *c, int split, PolarMixedTieredParams &t) {
     PolarMixedParams &m = t.m;
     m = c->mp;
-    const int nl = c->n;
     t.split = split;
     int grp = 0;
     for (int j = 0; j < split; ++j) {
@@ -535,24 +543,7 @@ void mixed_tiered_layout(const bchk_polar *c, int split, PolarMixedTieredParams 
     }
     t.grp_bytes = grp;
     m.coff[0] = 0;
-    int so = 0, co = 0, oo = 0;
-    for (int lam = split + 1; lam <= nl; ++lam) { m.soff[lam] = so; so += m.outer[lam]; }
-    for (int lam = split + 1; lam <= nl; ++lam) { m.coff[lam] = co; co += m.outer[lam] * c->ksize[lam - 1]; }
-    bool any_named = false;
-    for (int j = split; j < nl; ++j) {
-        m.ooff[j] = oo;
-        m.foff[j] = so;
-        if (c->named[j]) {
-            any_named = true;
-            so += polar_named_floats(c->named[j]) * m.outer[j + 1];
-            if (c->named[j] == kNamedA5) oo += m.outer[j + 1];
-        } else if (!c->arikan[j]) {
-            oo += c->ksize[j] * m.outer[j + 1];
-        }
-    }
-    m.ssize = so ? ((so + 3) & ~3) + (any_named ? 4 : 0) : 0;
-    m.csize = (co + 15) & ~15;
-    m.osize = (oo + 15) & ~15;
+    inner_layout(c, split, m);
 }
 PolarMixedTieredLayout mixed_tiered_lds(const bchk_polar *c, const PolarMixedTieredParams &t) {
     const PolarMixedParams &m = t.m;
@@ -562,6 +553,35 @@ size_t mixed_tiered_lds_at(const bchk_polar *c, int split) {
     PolarMixedTieredParams t{};
     mixed_tiered_layout(c, split, t);
     return mixed_tiered_lds(c, t).bytes;
+}
+
+// a workgroup's workspace in the state's layout (0: every path's state in LDS)
+uint64_t ws_bytes(const bchk_polar *c) {
+    switch (c->state) {
+    case State::ListTiered: return tiered_layout(c, c->split).ws_bytes;
+    case State::MixedTiered: return mixed_tiered_lds(c, c->tm).ws_bytes;
+    default: return 0;
+    }
+}
+// The split a tiered state chooses (counting layers from the channel side; lds_at(s): LDS bytes
+// at split s): the smallest whose LDS part fits, then further layers out while that lets one
+// more wave onto a CU (tiered_waves).
+template <class LdsAt>
+int auto_split(const bchk_polar *c, LdsAt lds_at) {
+    int s = 1;
+    while (s < c->n && lds_at(s) > kPolarLdsMax) ++s;
+    while (s < c->n && tiered_waves(lds_at(s + 1)) > tiered_waves(lds_at(s))) ++s;
+    return s;
+}
+// the state's kernel
+const void *kernel_ptr(State st) {
+    switch (st) {
+    case State::List: return polar_kernel_ptr();
+    case State::Mixed: return polar_mixed_kernel_ptr();
+    case State::ListTiered: return polar_tiered_kernel_ptr();
+    case State::MixedTiered: return polar_mixed_tiered_kernel_ptr();
+    }
+    return nullptr;
 }
 
 }  // namespace
@@ -582,34 +602,36 @@ int bchk_polar_create(const char *spec, int list_size, int device, bchk_polar **
     return bchk_polar_create_kdir(spec, nullptr, list_size, device, out);
 }
 
-// split: 0 = every path's state in LDS (bchk_polar_create_kdir); -1 or 1..n = tiered, through
-// the all-Arikan kernel or (tmixed) the mixed-kernel one
-static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bool tmixed,
+// want: List = every path's state in LDS, through the kernel the code needs (split 0); a tiered
+// state with split -1 (the library chooses) or 1..n
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, State want,
                         bchk_polar **out);
 
 int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out) {
-    return polar_create(spec, kdir, list_size, device, 0, false, out);
+    return polar_create(spec, kdir, list_size, device, 0, State::List, out);
+}
+
+// the checked entry of both tiered states
+static int polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split, State want,
+                               bchk_polar **out) {
+    if (split == 0 || split < -1) {
+        if (out) *out = nullptr;
+        return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
+    }
+    return polar_create(spec, kdir, list_size, device, split, want, out);
 }
 
 int bchk_polar_create_tiered_mixed(const char *spec, const char *kdir, int list_size, int device, int split,
                                    bchk_polar **out) {
-    if (split == 0 || split < -1) {
-        if (out) *out = nullptr;
-        return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
-    }
-    return polar_create(spec, kdir, list_size, device, split, true, out);
+    return polar_create_tiered(spec, kdir, list_size, device, split, State::MixedTiered, out);
 }
 
 int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
                              bchk_polar **out) {
-    if (split == 0 || split < -1) {
-        if (out) *out = nullptr;
-        return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..layers)", split);
-    }
-    return polar_create(spec, kdir, list_size, device, split, false, out);
+    return polar_create_tiered(spec, kdir, list_size, device, split, State::ListTiered, out);
 }
 
-static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, bool tmixed,
+static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, State want,
                         bchk_polar **out) {
     if (!out || !spec) return pfail(BCHK_EINVAL, "NULL argument");
     *out = nullptr;
@@ -621,35 +643,22 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
     c->L = list_size;
     c->device = device;
     if (int rc = parse_spec(c, spec, kdir)) return rc;
-    if (split && tmixed) {
+    if (want == State::MixedTiered) {
         if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
         if (int rc = mixed_tables(c)) return rc;
         if (c->mp.any_ml)
             return pfail(BCHK_EINVAL, "the tiered mixed state does not take a code with a search layer (a matrix kernel "
                                       "above %d, or BCHK_POLAR_ML): its save slots cover the LDS state", kPolarMaxTrellisKernel);
-        c->tmixed = true;
-        if (split < 0) {
-            // the rule of the all-Arikan tiered state on this layout, counting layers
-            int s = 1;
-            while (s < c->n && mixed_tiered_lds_at(c, s) > kPolarLdsMax) ++s;
-            while (s < c->n && tiered_waves(mixed_tiered_lds_at(c, s + 1)) > tiered_waves(mixed_tiered_lds_at(c, s))) ++s;
-            split = s;
-        }
+        c->state = State::MixedTiered;
+        if (split < 0) split = auto_split(c, [&](int s) { return mixed_tiered_lds_at(c, s); });
         c->split = split;
         mixed_tiered_layout(c, split, c->tm);
         c->lds = mixed_tiered_lds(c, c->tm).bytes;
-    } else if (split) {
+    } else if (want == State::ListTiered) {
         if (c->mixed) return pfail(BCHK_EINVAL, "tiered state is built for all-Arikan codes (a matrix or named layer)");
         if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
-        c->tiered = true;
-        if (split < 0) {
-            // the smallest split whose LDS part fits, then further layers out while that lets
-            // one more wave onto a CU (tiered_waves)
-            int s = 1;
-            while (s < c->n && tiered_layout(c, s).bytes > kPolarLdsMax) ++s;
-            while (s < c->n && tiered_waves(tiered_layout(c, s + 1).bytes) > tiered_waves(tiered_layout(c, s).bytes)) ++s;
-            split = s;
-        }
+        c->state = State::ListTiered;
+        if (split < 0) split = auto_split(c, [&](int s) { return (size_t)tiered_layout(c, s).bytes; });
         c->split = split;
         int32_t off[kPolarMaxLayers + 1];
         (void)polar_cw_layout(c->U, off);
@@ -658,12 +667,13 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         c->lds = tiered_layout(c, split).bytes;
     } else if (c->mixed) {
         if (int rc = mixed_tables(c)) return rc;
+        c->state = State::Mixed;
         c->lds = mixed_lds(c).bytes;
     } else {
         c->lds = polar_list_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     }
     if (c->lds > kPolarLdsMax) {
-        if (c->tiered || c->tmixed)
+        if (c->is_tiered())
             return pfail(BCHK_EINVAL, "length %d with list %d at split %d still needs %zu B of LDS (> 160 KiB)", c->U,
                          list_size, c->split, c->lds);
         return pfail(BCHK_EINVAL, "length %d with list %d needs %zu B of LDS (> 160 KiB)", c->U, list_size, c->lds);
@@ -711,19 +721,19 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         hipMemcpy(c->d_tab, blob.data(), o, hipMemcpyHostToDevice) != hipSuccess ||
         hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess)
         return pfail(BCHK_EHIP, "device setup failed");
-    const void *fn = c->tmixed ? polar_mixed_tiered_kernel_ptr() : c->tiered ? polar_tiered_kernel_ptr() : c->mixed ? polar_mixed_kernel_ptr() : polar_kernel_ptr();
+    const void *fn = kernel_ptr(c->state);
     if (c->lds > 65536) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c->lds);
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64, c->lds) != hipSuccess || per_cu <= 0) {
         per_cu = 1;
         (void)hipGetLastError();
     }
-    if (c->tiered || c->tmixed) per_cu = std::min(per_cu, kTieredWaves);
+    if (c->is_tiered()) per_cu = std::min(per_cu, kTieredWaves);
     c->grid = polar_grid("bchk_polar", c, c->lds, per_cu, prop.multiProcessorCount);
-    if (c->tiered || c->tmixed) {
+    if (c->is_tiered()) {
         // one workspace per workgroup, allocated once; the grid shrinks to keep them within the
         // bound (BCHK_POLAR_WORKSPACE_MB, default 1024), down to a single workgroup
-        const uint64_t per_wg = c->tmixed ? mixed_tiered_lds(c, c->tm).ws_bytes : tiered_layout(c, c->split).ws_bytes;
+        const uint64_t per_wg = ws_bytes(c);
         int mb = 1024;
         env_int("BCHK_POLAR_WORKSPACE_MB", &mb, 1, 1 << 20);
         const uint64_t fit = ((uint64_t)mb << 20) / per_wg;
@@ -735,7 +745,7 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
     }
     // codes with search layers: launches of at most ~50 ms (BCHK_POLAR_BUDGET_MS, 0 = one
     // launch per call), so no launch holds the GPU for seconds
-    if (c->mixed && c->mp.any_ml && !c->tmixed) {
+    if (c->state == State::Mixed && c->mp.any_ml) {
         double ms = 50.0;
         env_double("BCHK_POLAR_BUDGET_MS", &ms, 0.0, DBL_MAX);
         c->budget_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
@@ -778,113 +788,115 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
     if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
     if (B == 0) return 0;
     if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
-    PolarParams p{};
-    p.llr = d_llr;
-    p.info = d_info;
-    p.cw = d_cw;
-    p.metric = d_metric;
-    p.count = d_count;
-    p.symmap = reinterpret_cast<const int16_t *>(c->d_tab + c->off_symmap);
-    p.phase = reinterpret_cast<const uint16_t *>(c->d_tab + c->off_phase);
-    p.cwpos = reinterpret_cast<const int16_t *>(c->d_tab + c->off_cwpos);
-    p.dfcorr = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_dfcorr);
-    p.B = (uint32_t)B;
-    p.pathCw = polar_cw_layout(c->U, p.cwoff);
-    p.n = c->n;
-    p.U = c->U;
-    p.N = c->N;
-    p.K = c->K;
-    p.L = c->L;
-    const int grid = (int)std::min<size_t>((size_t)c->grid, B);
-    if (c->mixed || c->tmixed) {
-        PolarMixedTieredParams t = c->tm;  // (tmixed; grid <= the workspaces allocated at create)
-        PolarMixedParams &m = t.m;
-        if (!c->tmixed) m = c->mp;
-        m.llr = p.llr;
-        m.info = p.info;
-        m.cw = p.cw;
-        m.metric = p.metric;
-        m.count = p.count;
-        m.symmap = p.symmap;
-        m.phase = p.phase;
-        m.dfcorr = p.dfcorr;
-        m.cwpos = p.cwpos;
+    PolarIo io{};
+    io.llr = d_llr;
+    io.info = d_info;
+    io.cw = d_cw;
+    io.metric = d_metric;
+    io.count = d_count;
+    io.symmap = reinterpret_cast<const int16_t *>(c->d_tab + c->off_symmap);
+    io.phase = reinterpret_cast<const uint16_t *>(c->d_tab + c->off_phase);
+    io.cwpos = reinterpret_cast<const int16_t *>(c->d_tab + c->off_cwpos);
+    io.dfcorr = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_dfcorr);
+    const int grid = (int)std::min<size_t>((size_t)c->grid, B);  // tiered: <= the workspaces allocated at create
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    auto list_params = [&]() {
+        PolarParams p{};
+        p.io = io;
+        p.B = (uint32_t)B;
+        p.pathCw = polar_cw_layout(c->U, p.cwoff);
+        p.n = c->n;
+        p.U = c->U;
+        p.N = c->N;
+        p.K = c->K;
+        p.L = c->L;
+        return p;
+    };
+    auto mixed_params = [&](PolarMixedParams m) {  // m: the state's layout
+        m.io = io;
         m.krows = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_krows);
         m.tent = reinterpret_cast<const uint32_t *>(c->d_tab + c->off_tent);
         m.tbase = reinterpret_cast<const uint32_t *>(c->d_tab + c->off_tbase);
         m.tlog = c->d_tab + c->off_tlog;
-        m.B = p.B;
+        m.B = (uint32_t)B;
         m.U = c->U;
         m.N = c->N;
         m.K = c->K;
         m.L = c->L;
-        hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-        if (c->tmixed) {
-            t.ws = (uint8_t *)c->ws.p;
-            PHIP_TRY(launch_polar_mixed_tiered(t, grid, c->lds, s));
-            return 0;
-        }
-        if (!(m.any_ml && c->budget_ticks)) {
-            PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
-            return 0;
-        }
-        // Codes with search layers: one codeword's list decode can run for seconds (every
-        // phase's search items in one wave), so the call is a series of launches of at most
-        // ~budget each (plus one search item): a wave suspends its codeword between two items
-        // past the budget and the next launch resumes it (same results, bit for bit: the
-        // state saved is the whole list state). The call returns when every codeword is done.
-        // A workgroup has at most one suspended codeword (PolarMixedParams), and the grid is
-        // the same for every launch of the call: one save slot per workgroup.
-        const uint32_t stride = mixed_lds(c).save_bytes;
-        int rc;
-        if ((rc = c->rstate.ensure(B * 4)) || (rc = c->rsave.ensure((size_t)grid * stride)) ||
-            (rc = c->unfinished.ensure(8)))
-            return rc;
-        PHIP_TRY(hipMemsetAsync(c->rstate.p, 0, B * 4, s));
-        m.rstate = (uint32_t *)c->rstate.p;
-        m.rsave = (uint8_t *)c->rsave.p;
-        m.rstride = stride;
-        m.unfinished = (uint32_t *)c->unfinished.p;  // two words: unfinished, progress
-        m.progress = m.unfinished + 1;
-        m.budget = c->budget_ticks;
-        m.no_mid = env_flag("BCHK_POLAR_NO_MID") ? 1 : 0;  // per call: tests toggle it on a live context
-        for (uint64_t launch = 0;; ++launch) {
-            PHIP_TRY(hipMemsetAsync(c->unfinished.p, 0, 8, s));
-            PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
-            uint32_t left[2] = {0, 0};
-            PHIP_TRY(hipMemcpyAsync(left, c->unfinished.p, 8, hipMemcpyDeviceToHost, s));
-            PHIP_TRY(hipStreamSynchronize(s));
-            c->launches_last = launch + 1;
-            if (left[0] == 0) break;
-            // every launch that leaves work does some (the kernel starts or resumes a wave's
-            // first unfinished codeword whatever the clock says): no progress is a kernel fault,
-            // reported instead of launching for ever
-            if (left[1] == 0)
-                return pfail(BCHK_EHIP, "budgeted SC-list decode made no progress in launch %llu (%u codewords left)",
-                             (unsigned long long)(launch + 1), left[0]);
-        }
+        return m;
+    };
+    switch (c->state) {
+    case State::List:
+        PHIP_TRY(launch_polar(list_params(), grid, c->lds, s));
         return 0;
-    }
-    if (c->tiered) {  // grid <= the workspaces allocated at create
+    case State::ListTiered: {
         PolarTieredParams t{};
-        t.p = p;
+        t.p = list_params();
         t.ws = (uint8_t *)c->ws.p;
         t.split = c->split;
         t.cwsplit = c->cwsplit;
         t.cwall = c->cwall;
-        PHIP_TRY(launch_polar_tiered(t, grid, c->lds, stream ? (hipStream_t)stream : c->stream));
+        PHIP_TRY(launch_polar_tiered(t, grid, c->lds, s));
         return 0;
     }
-    PHIP_TRY(launch_polar(p, grid, c->lds, stream ? (hipStream_t)stream : c->stream));
+    case State::MixedTiered: {
+        PolarMixedTieredParams t = c->tm;
+        t.m = mixed_params(c->tm.m);
+        t.ws = (uint8_t *)c->ws.p;
+        PHIP_TRY(launch_polar_mixed_tiered(t, grid, c->lds, s));
+        return 0;
+    }
+    case State::Mixed:
+        break;
+    }
+    PolarMixedParams m = mixed_params(c->mp);
+    if (!(m.any_ml && c->budget_ticks)) {
+        PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
+        return 0;
+    }
+    // Codes with search layers: one codeword's list decode can run for seconds (every
+    // phase's search items in one wave), so the call is a series of launches of at most
+    // ~budget each (plus one search item): a wave suspends its codeword between two items
+    // past the budget and the next launch resumes it (same results, bit for bit: the
+    // state saved is the whole list state). The call returns when every codeword is done.
+    // A workgroup has at most one suspended codeword (PolarMixedParams), and the grid is
+    // the same for every launch of the call: one save slot per workgroup.
+    const uint32_t stride = mixed_lds(c).save_bytes;
+    int rc;
+    if ((rc = c->rstate.ensure(B * 4)) || (rc = c->rsave.ensure((size_t)grid * stride)) ||
+        (rc = c->unfinished.ensure(8)))
+        return rc;
+    PHIP_TRY(hipMemsetAsync(c->rstate.p, 0, B * 4, s));
+    m.rstate = (uint32_t *)c->rstate.p;
+    m.rsave = (uint8_t *)c->rsave.p;
+    m.rstride = stride;
+    m.unfinished = (uint32_t *)c->unfinished.p;  // two words: unfinished, progress
+    m.progress = m.unfinished + 1;
+    m.budget = c->budget_ticks;
+    m.no_mid = env_flag("BCHK_POLAR_NO_MID") ? 1 : 0;  // per call: tests toggle it on a live context
+    for (uint64_t launch = 0;; ++launch) {
+        PHIP_TRY(hipMemsetAsync(c->unfinished.p, 0, 8, s));
+        PHIP_TRY(launch_polar_mixed(m, grid, c->lds, s));
+        uint32_t left[2] = {0, 0};
+        PHIP_TRY(hipMemcpyAsync(left, c->unfinished.p, 8, hipMemcpyDeviceToHost, s));
+        PHIP_TRY(hipStreamSynchronize(s));
+        c->launches_last = launch + 1;
+        if (left[0] == 0) break;
+        // every launch that leaves work does some (the kernel starts or resumes a wave's
+        // first unfinished codeword whatever the clock says): no progress is a kernel fault,
+        // reported instead of launching for ever
+        if (left[1] == 0)
+            return pfail(BCHK_EHIP, "budgeted SC-list decode made no progress in launch %llu (%u codewords left)",
+                         (unsigned long long)(launch + 1), left[0]);
+    }
     return 0;
 }
 
 int bchk_polar_state_info(const bchk_polar *c, int *split, uint64_t *lds_bytes, uint64_t *workspace_bytes, int *grid) {
     if (!c) return pfail(BCHK_EINVAL, "NULL argument");
-    if (split) *split = (c->tiered || c->tmixed) ? c->split : 0;
+    if (split) *split = c->is_tiered() ? c->split : 0;
     if (lds_bytes) *lds_bytes = c->lds;
-    if (workspace_bytes)
-        *workspace_bytes = c->tmixed ? mixed_tiered_lds(c, c->tm).ws_bytes : c->tiered ? tiered_layout(c, c->split).ws_bytes : 0;
+    if (workspace_bytes) *workspace_bytes = ws_bytes(c);
     if (grid) *grid = c->grid;
     return 0;
 }

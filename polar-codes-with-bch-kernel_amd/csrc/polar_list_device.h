@@ -2,8 +2,10 @@
 // kernels (polar_sclist.hip, polar_sclist_tiered.hip) and the mixed-kernel ones (polar_mixed.hip, polar_mixed_tiered.hip): one copy of the
 // reference's CMixedKernelListDecoder (out/external/MixedKernelListDecoder.cpp:61-268) over the
 // path-index stack of out/external/TVMemoryEngine.cpp:85-142, so both kernels take the same
-// decisions with the same tie-breaks and path indices. Also the wave barrier of every polar
-// kernel.
+// decisions with the same tie-breaks and path indices. Also LoadLLRs (chan_llr, every polar
+// kernel's) and the wave barrier of every polar kernel. SoftXOR and the mixed kernels' LLR
+// routines are in polar_llr_device.h, the tiered kernels' index-table lines in
+// polar_tier_device.h. The epilogues stay in the kernels.
 //
 // One wave per codeword. Lane q < L holds path q's scalars (PathRegs) and slot q of the
 // path-index stack in registers; `active` (bit q = path q alive), the stack's top and the
@@ -174,6 +176,13 @@ __device__ __forceinline__ void record_decision(bool now, uint32_t dec, PathRegs
 __device__ __forceinline__ void flush_record(const PathRegs &r, int k, bool now, uint32_t *rec, int RW, int lane) {
     if ((k & 31) && now) rec[lane * RW + (k >> 5)] = r.rw;
     wsync();
+}
+
+// ---- LoadLLRs (MixedKernelEncoder.cpp:181-207): symbol i of the unshortened code from the
+// caller's row y; a shortened symbol is a certain 0, a punctured one an erasure.
+__device__ __forceinline__ float chan_llr(const int16_t *symmap, const float *y, int i) {
+    const int m = symmap[i];
+    return m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
 }
 
 }  // namespace plist

@@ -8,7 +8,8 @@
 // `phase` is the min-sum difference best[1] - best[0] over the coset of the remaining rows,
 // by coset enumeration or by the pull-form Viterbi over the trellis. Named layers (G, A5):
 // the recursive f/g processors of TruncatedArikanKernel.cpp with their per-path state. Partial
-// sums: IterativelyUpdateC (KernelListEngine.cpp:266-315).
+// sums: IterativelyUpdateC (KernelListEngine.cpp:266-315). soft_xor is the only SoftXOR of the
+// polar kernels: the all-Arikan kernels (polar_sclist.hip, polar_sclist_tiered.hip) call it too.
 //
 // The routines run on one wave. Work items are (path, element) pairs, it = k * d + s with k
 // an index into the caller's active paths: pathof(k) is the path, Sof(q, λ) its LLRs of layer
@@ -50,6 +51,14 @@ __device__ __forceinline__ void coset_min(const uint64_t *rows, int l, int phase
     }
 }
 
+// SoftXOR and SoftCombine of one element (SoftProcessing.cpp:54-80, :39-50): the one spelling of
+// both in the polar kernels. SoftXOR: sign(a) sign(b) min(|a|, |b|)
+__device__ __forceinline__ float soft_xor(float a, float b) {
+    const float fa = fabsf(a), fb = fabsf(b), mn = fa < fb ? fa : fb;
+    return __uint_as_float(__float_as_uint(mn) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
+}
+__device__ __forceinline__ float soft_combine(float a, float b, uint32_t c) { return c ? b - a : b + a; }
+
 // Arikan layer j at local phase loc: S_{j+1} from S_j (d = outer[j + 1] elements per path)
 template <class PathOf, class SOf, class COf>
 __device__ __forceinline__ void arikan_llrs(int j, int loc, int d, int tot, int lane, PathOf pathof, SOf Sof,
@@ -59,23 +68,9 @@ __device__ __forceinline__ void arikan_llrs(int j, int loc, int d, int tot, int 
         const float *src = Sof(q, j);
         float *dst = Sof(q, j + 1);
         const float a = src[s], b = src[d + s];
-        float r;
-        if (loc) {  // SoftCombine (:39-50)
-            r = Cof(q, j + 1)[s] ? b - a : b + a;
-        } else {    // SoftXOR (:54-80)
-            const float fa = fabsf(a), fb = fabsf(b), mn = fa < fb ? fa : fb;
-            r = __uint_as_float(__float_as_uint(mn) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-        }
-        dst[s] = r;
+        dst[s] = loc ? soft_combine(a, b, Cof(q, j + 1)[s]) : soft_xor(a, b);
     }
 }
-
-// SoftXOR and SoftCombine of one element (SoftProcessing.cpp:54-80, :39-50), spelled as above
-__device__ __forceinline__ float soft_xor(float a, float b) {
-    const float fa = fabsf(a), fb = fabsf(b), mn = fa < fb ? fa : fb;
-    return __uint_as_float(__float_as_uint(mn) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-}
-__device__ __forceinline__ float soft_combine(float a, float b, uint32_t c) { return c ? b - a : b + a; }
 
 // Named layer j (kind kNamedG / kNamedA5, polar_device.h) at local phase loc:
 // CGKernelProcessor::GetLLRs and CA5KernelProcessor::GetLLRs (out/external/

@@ -356,7 +356,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
     uint8_t *mls = smem + lo.o_ml;  // ordered-statistics search scratch
     const MlScratch ms(mls);
     const bool mine = lane < L;
-    for (int i = lane; i < U; i += 64) ph[i] = p.phase[i];
+    for (int i = lane; i < U; i += 64) ph[i] = p.io.phase[i];
     for (int i = lane; i < kPolarMaxKernel * nl; i += 64) rows[i] = p.krows[i];
     auto Sof = [&](int q, int lam) -> float * { return lam == 0 ? chan : S + (size_t)q * p.ssize + p.soff[lam]; };
     auto Cof = [&](int q, int lam) -> uint8_t * { return C + (size_t)q * p.csize + p.coff[lam]; };
@@ -414,11 +414,8 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
                 slot_search<false>(sv, mls, lo, mr.sp, lane);
             }
         } else {
-            const float *y = p.llr + (size_t)cw * p.N;  // LoadLLRs (MixedKernelEncoder.cpp:181-207)
-            for (int i = lane; i < U; i += 64) {
-                const int m = p.symmap[i];
-                chan[i] = m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
-            }
+            const float *y = p.io.llr + (size_t)cw * p.N;  // LoadLLRs (MixedKernelEncoder.cpp:181-207)
+            for (int i = lane; i < U; i += 64) chan[i] = chan_llr(p.io.symmap, y, i);
             st.reset(L, lane);
             const uint32_t pid = st.pop(lane);
             active = 1u << pid;
@@ -513,7 +510,7 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             if (yielded) break;
             const bool on = mine && ((active >> lane) & 1u);
             if (on) pr.lv = Sof(lane, nl)[0];
-            const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
+            const uint64_t corr = (e & kPhaseCorr) ? p.io.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
             if (e & kPhaseFrozen) {
                 dec = frozen_step(e, on, pr);
@@ -561,12 +558,12 @@ __global__ void __launch_bounds__(64) polar_mixed_kernel(PolarMixedParams p) {
             const uint8_t *cq = C + (size_t)q * p.csize;  // C_0: the unshortened codeword
             const uint32_t *rq = rec + q * RW;
             const size_t row = (size_t)cw * L + r;
-            for (int kk = lane; kk < K; kk += 64) p.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
-            if (p.cw)
-                for (int i = lane; i < p.N; i += 64) p.cw[row * p.N + i] = cq[p.cwpos[i]];
-            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
+            for (int kk = lane; kk < K; kk += 64) p.io.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
+            if (p.io.cw)
+                for (int i = lane; i < p.N; i += 64) p.io.cw[row * p.N + i] = cq[p.io.cwpos[i]];
+            if (lane == 0) p.io.metric[row] = rdl_f(pr.R, q);
         }
-        if (lane == 0) p.count[cw] = nact;
+        if (lane == 0) p.io.count[cw] = nact;
         if (budgeted && lane == 0) {
             p.rstate[cw] = 2u;
             atomicAdd(p.progress, prog + 1u);

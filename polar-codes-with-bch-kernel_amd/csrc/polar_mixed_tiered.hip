@@ -31,6 +31,9 @@
 // Array indices only select memory: every order and tie-break is on path indices.
 // `j < split` is wave-uniform and branched on, so each call of a routine sees one address space
 // per argument: LDS accesses stay ds_*, workspace accesses global_* (none flat).
+// Shared text: LoadLLRs (plist::chan_llr), SoftXOR (pllr::soft_xor) and the index table's
+// tier_init / tier_clone (polar_tier_device.h); own_group is the twin of the other tiered kernel's
+// routine, kept apart by the speed gate of DESIGN 5.17.
 // No MFMA: float min/add and byte XOR on short vectors, plain vector loads and stores.
 #include <hip/hip_runtime.h>
 
@@ -39,6 +42,7 @@
 #include "polar_device.h"
 #include "polar_list_device.h"
 #include "polar_llr_device.h"
+#include "polar_tier_device.h"
 
 namespace bchk {
 
@@ -69,7 +73,7 @@ __global__ void __launch_bounds__(64) polar_mixed_tiered_kernel(PolarMixedTiered
     uint8_t *G = wsb + lo.w_grp;
     const bool mine = lane < L;
     const uint32_t lmask = L >= 32 ? 0xFFFFFFFFu : (1u << L) - 1u;
-    for (int i = lane; i < U; i += 64) ph[i] = p.phase[i];
+    for (int i = lane; i < U; i += 64) ph[i] = p.io.phase[i];
     for (int i = lane; i < kPolarMaxKernel * nl; i += 64) rows[i] = p.krows[i];
 
     // the global tier: path q's array of group j, and its parts (S_0: the channel; C_0: the path's own)
@@ -163,18 +167,15 @@ __global__ void __launch_bounds__(64) polar_mixed_tiered_kernel(PolarMixedTiered
     wsync();
     for (uint32_t cw = blockIdx.x; cw < p.B; cw += gridDim.x) {
         // ---- LoadLLRs (MixedKernelEncoder.cpp:181-207), from the caller's row into the workspace
-        const float *y = p.llr + (size_t)cw * p.N;
-        for (int i = lane; i < U; i += 64) {
-            const int m = p.symmap[i];
-            chan[i] = m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
-        }
+        const float *y = p.io.llr + (size_t)cw * p.N;
+        for (int i = lane; i < U; i += 64) chan[i] = chan_llr(p.io.symmap, y, i);
         // the initial path names array 0 of every group, whatever the last codeword left
         st.reset(L, lane);
         const uint32_t pid = st.pop(lane);
         uint32_t active = 1u << pid;
         PathRegs pr{0.0f, 0.0f, 0ull, 0u};
         int k = 0;
-        if (lane < sp) idx[lane * L + (int)pid] = 0;
+        ptier::tier_init(idx, sp, L, pid, lane);
         wsync();
         int nact = list_active(active, act, lane, L);
         for (int phi = 0; phi < U; ++phi) {
@@ -207,7 +208,7 @@ __global__ void __launch_bounds__(64) polar_mixed_tiered_kernel(PolarMixedTiered
                 else
                     pr.lv = lS(lane, nl)[0];
             }
-            const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
+            const uint64_t corr = (e & kPhaseCorr) ? p.io.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
             if (e & kPhaseFrozen) {
                 dec = frozen_step(e, on, pr);
@@ -218,7 +219,7 @@ __global__ void __launch_bounds__(64) polar_mixed_tiered_kernel(PolarMixedTiered
                 for (uint32_t cl = ct.clones; cl; cl &= cl - 1) {
                     const int l = __builtin_ctz(cl);
                     const int l1 = (int)st.pop(lane);  // ClonePath: l1 names l's global arrays ...
-                    if (lane < sp) idx[lane * L + l1] = idx[lane * L + l];
+                    ptier::tier_clone(idx, sp, L, l, l1, lane);
                     // ... and copies its LDS state
                     for (int i = lane; i < p.ssize; i += 64) S[(size_t)l1 * p.ssize + i] = S[(size_t)l * p.ssize + i];
                     for (int i = lane; i < p.csize; i += 64) C[(size_t)l1 * p.csize + i] = C[(size_t)l * p.csize + i];
@@ -286,12 +287,12 @@ __global__ void __launch_bounds__(64) polar_mixed_tiered_kernel(PolarMixedTiered
             const uint8_t *cq = C0 + (size_t)q * lo.c0;  // C_0: the unshortened codeword
             const uint32_t *rq = rec + q * RW;
             const size_t row = (size_t)cw * L + r;
-            for (int kk = lane; kk < K; kk += 64) p.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
-            if (p.cw)
-                for (int i = lane; i < p.N; i += 64) p.cw[row * p.N + i] = cq[p.cwpos[i]];
-            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
+            for (int kk = lane; kk < K; kk += 64) p.io.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
+            if (p.io.cw)
+                for (int i = lane; i < p.N; i += 64) p.io.cw[row * p.N + i] = cq[p.io.cwpos[i]];
+            if (lane == 0) p.io.metric[row] = rdl_f(pr.R, q);
         }
-        if (lane == 0) p.count[cw] = nact;
+        if (lane == 0) p.io.count[cw] = nact;
         wsync();
     }
 }

@@ -29,6 +29,7 @@
 
 #include "polar_device.h"
 #include "polar_list_device.h"
+#include "polar_llr_device.h"
 
 namespace bchk {
 
@@ -38,13 +39,6 @@ using namespace plist;
 
 // offset of S_λ (λ >= 1) inside one path's LLR array
 __device__ __forceinline__ int s_off(int U, int lam) { return U - (U >> (lam - 1)); }
-
-// SoftXOR (SoftProcessing.cpp:54-80): sign(a) sign(b) min(|a|, |b|)
-__device__ __forceinline__ float f_minsum(float a, float b) {
-    const float fa = fabsf(a), fb = fabsf(b);
-    const float m = fa < fb ? fa : fb;
-    return __uint_as_float(__float_as_uint(m) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-}
 
 }  // namespace
 
@@ -72,11 +66,8 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
     st.slot = 0;
     for (uint32_t cw = blockIdx.x; cw < p.B; cw += gridDim.x) {
         // ---- LoadLLRs (MixedKernelEncoder.cpp:181-207), applied where layer 0 is read
-        const float *y = p.llr + (size_t)cw * p.N;
-        auto chan = [&](int i) -> float {
-            const int m = p.symmap[i];
-            return m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
-        };
+        const float *y = p.io.llr + (size_t)cw * p.N;
+        auto chan = [&](int i) -> float { return chan_llr(p.io.symmap, y, i); };
         // ---- Cleanup + AssignInitialPath (TVMemoryEngine.cpp:58-94)
         st.reset(L, lane);
         const uint32_t pid = st.pop(lane);
@@ -87,7 +78,7 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
         int nact = list_active(active, act, lane, L);
 
         for (int phi = 0; phi < U; ++phi) {
-            const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)p.phase[phi]);
+            const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)p.io.phase[phi]);
             // ---- IterativelyCalcS (KernelListEngine.cpp:370-447): from layer m, where the
             // block of phase phi starts, down to the single LLR of layer n
             int m = 0, local = 0;
@@ -116,7 +107,7 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
                     if (loc) {  // SoftCombine (:39-50): b - a if u = 1 else b + a
                         r = cbit(q, j + 1, s) ? b - a : b + a;
                     } else {
-                        r = f_minsum(a, b);
+                        r = pllr::soft_xor(a, b);
                     }
                     dst[s] = r;
                 }
@@ -124,7 +115,7 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
             }
             const bool on = mine && ((active >> lane) & 1u);
             if (on) pr.lv = S[(size_t)lane * pathS + U - 2];
-            const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
+            const uint64_t corr = (e & kPhaseCorr) ? p.io.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
 
             if (e & kPhaseFrozen) {
@@ -231,33 +222,33 @@ __global__ void __launch_bounds__(64) polar_sclist_kernel(PolarParams p) {
             const uint32_t *rq = rec + q * RW;
             const size_t row = (size_t)cw * L + r;
             if ((K & 3) == 0) {  // information bits, four per lane and store
-                uint32_t *o4 = reinterpret_cast<uint32_t *>(p.info + row * K);
+                uint32_t *o4 = reinterpret_cast<uint32_t *>(p.io.info + row * K);
                 for (int w = lane; w < (K >> 2); w += 64) {
                     const uint32_t bits = (rq[w >> 3] >> ((w & 7) * 4)) & 15u;
                     o4[w] = (bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21);
                 }
             } else {
-                for (int kk = lane; kk < K; kk += 64) p.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
+                for (int kk = lane; kk < K; kk += 64) p.io.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
             }
-            if (p.cw) {
+            if (p.io.cw) {
                 if ((p.N & 3) == 0) {
-                    uint32_t *o4 = reinterpret_cast<uint32_t *>(p.cw + row * p.N);
+                    uint32_t *o4 = reinterpret_cast<uint32_t *>(p.io.cw + row * p.N);
                     for (int w = lane; w < (p.N >> 2); w += 64) {
                         const int i0 = 4 * w;
                         auto bitat = [&](int i) { return (cq[i >> 5] >> (i & 31)) & 1u; };
-                        o4[w] = bitat(p.cwpos[i0]) | (bitat(p.cwpos[i0 + 1]) << 8) |
-                                (bitat(p.cwpos[i0 + 2]) << 16) | (bitat(p.cwpos[i0 + 3]) << 24);
+                        o4[w] = bitat(p.io.cwpos[i0]) | (bitat(p.io.cwpos[i0 + 1]) << 8) |
+                                (bitat(p.io.cwpos[i0 + 2]) << 16) | (bitat(p.io.cwpos[i0 + 3]) << 24);
                     }
                 } else {
                     for (int i = lane; i < p.N; i += 64) {
-                        const int ci = p.cwpos[i];
-                        p.cw[row * p.N + i] = (uint8_t)((cq[ci >> 5] >> (ci & 31)) & 1u);
+                        const int ci = p.io.cwpos[i];
+                        p.io.cw[row * p.N + i] = (uint8_t)((cq[ci >> 5] >> (ci & 31)) & 1u);
                     }
                 }
             }
-            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
+            if (lane == 0) p.io.metric[row] = rdl_f(pr.R, q);
         }
-        if (lane == 0) p.count[cw] = nact;
+        if (lane == 0) p.io.count[cw] = nact;
         wsync();
     }
 }

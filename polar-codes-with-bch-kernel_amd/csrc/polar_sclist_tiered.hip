@@ -22,6 +22,9 @@
 // nothing of S (f / g rewrite the whole layer), and of C the first half when the second is the
 // one being written (or about to be read by g); the other cases leave nothing live. Array
 // indices only select memory: every order and tie-break is on path indices.
+// Shared text: LoadLLRs (plist::chan_llr), SoftXOR (pllr::soft_xor) and the index table's
+// tier_init / tier_clone (polar_tier_device.h); own_layer is the twin of the other tiered kernel's
+// routine, kept apart by the speed gate of DESIGN 5.17.
 // No MFMA: float min/add and word XOR on short vectors, plain vector loads and stores.
 #include <hip/hip_runtime.h>
 
@@ -29,19 +32,14 @@
 
 #include "polar_device.h"
 #include "polar_list_device.h"
+#include "polar_llr_device.h"
+#include "polar_tier_device.h"
 
 namespace bchk {
 
 namespace {
 
 using namespace plist;
-
-// SoftXOR (SoftProcessing.cpp:54-80): sign(a) sign(b) min(|a|, |b|)
-__device__ __forceinline__ float f_minsum_t(float a, float b) {
-    const float fa = fabsf(a), fb = fabsf(b);
-    const float m = fa < fb ? fa : fb;
-    return __uint_as_float(__float_as_uint(m) | ((__float_as_uint(a) ^ __float_as_uint(b)) & 0x80000000u));
-}
 
 }  // namespace
 
@@ -125,7 +123,7 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
             if (loc) {  // SoftCombine (:39-50): b - a if u = 1 else b + a
                 r = ((cw(q)[s >> 5] >> (s & 31)) & 1u) ? b - a : b + a;
             } else {
-                r = f_minsum_t(a, b);
+                r = pllr::soft_xor(a, b);
             }
             dst(q)[s] = r;
         }
@@ -165,11 +163,8 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
     st.slot = 0;
     for (uint32_t cw = blockIdx.x; cw < p.B; cw += gridDim.x) {
         // ---- LoadLLRs (MixedKernelEncoder.cpp:181-207), applied where layer 0 is read
-        const float *y = p.llr + (size_t)cw * p.N;
-        auto chan = [&](int i) -> float {
-            const int m = p.symmap[i];
-            return m >= 0 ? y[m] : (m == -1 ? 100000.0f : 0.0f);
-        };
+        const float *y = p.io.llr + (size_t)cw * p.N;
+        auto chan = [&](int i) -> float { return chan_llr(p.io.symmap, y, i); };
         // ---- Cleanup + AssignInitialPath (TVMemoryEngine.cpp:58-94); the initial path names
         // array 0 of every global layer, whatever the last codeword left
         st.reset(L, lane);
@@ -177,12 +172,12 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
         uint32_t active = 1u << pid;
         PathRegs pr{0.0f, 0.0f, 0ull, 0u};
         int k = 0;  // unfrozen decisions so far
-        if (lane < sp) idx[lane * L + (int)pid] = 0;
+        ptier::tier_init(idx, sp, L, pid, lane);
         wsync();
         int nact = list_active(active, act, lane, L);
 
         for (int phi = 0; phi < U; ++phi) {
-            const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)p.phase[phi]);
+            const uint32_t e = __builtin_amdgcn_readfirstlane((uint32_t)p.io.phase[phi]);
             const bool on = mine && ((active >> lane) & 1u);
             // ---- IterativelyCalcS (KernelListEngine.cpp:370-447): from layer m, where the
             // block of phase phi starts, down to the single LLR of layer n
@@ -218,7 +213,7 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
                 else
                     pr.lv = lS(n, lane)[0];
             }
-            const uint64_t corr = (e & kPhaseCorr) ? p.dfcorr[phi] : 0ull;
+            const uint64_t corr = (e & kPhaseCorr) ? p.io.dfcorr[phi] : 0ull;
             uint32_t dec = 0;
 
             if (e & kPhaseFrozen) {
@@ -230,7 +225,7 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
                 for (uint32_t cl = ct.clones; cl; cl &= cl - 1) {
                     const int l = __builtin_ctz(cl);
                     const int l1 = (int)st.pop(lane);  // ClonePath: l1 names l's global arrays ...
-                    if (lane < sp) idx[lane * L + l1] = idx[lane * L + l];
+                    ptier::tier_clone(idx, sp, L, l, l1, lane);
                     {
                         // ... and copies the live state of l in LDS: S_j (j > split) is read
                         // again iff bit n-1-j of phi is 0, from the first such layer on; the
@@ -318,33 +313,33 @@ __global__ void __launch_bounds__(64) polar_sclist_tiered_kernel(PolarTieredPara
             const uint32_t *rq = rec + q * RW;
             const size_t row = (size_t)cw * L + r;
             if ((K & 3) == 0) {  // information bits, four per lane and store
-                uint32_t *o4 = reinterpret_cast<uint32_t *>(p.info + row * K);
+                uint32_t *o4 = reinterpret_cast<uint32_t *>(p.io.info + row * K);
                 for (int w = lane; w < (K >> 2); w += 64) {
                     const uint32_t bits = (rq[w >> 3] >> ((w & 7) * 4)) & 15u;
                     o4[w] = (bits & 1u) | ((bits & 2u) << 7) | ((bits & 4u) << 14) | ((bits & 8u) << 21);
                 }
             } else {
-                for (int kk = lane; kk < K; kk += 64) p.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
+                for (int kk = lane; kk < K; kk += 64) p.io.info[row * K + kk] = (uint8_t)((rq[kk >> 5] >> (kk & 31)) & 1u);
             }
-            if (p.cw) {
+            if (p.io.cw) {
                 if ((p.N & 3) == 0) {
-                    uint32_t *o4 = reinterpret_cast<uint32_t *>(p.cw + row * p.N);
+                    uint32_t *o4 = reinterpret_cast<uint32_t *>(p.io.cw + row * p.N);
                     for (int w = lane; w < (p.N >> 2); w += 64) {
                         const int i0 = 4 * w;
                         auto bitat = [&](int i) { return (cq[i >> 5] >> (i & 31)) & 1u; };
-                        o4[w] = bitat(p.cwpos[i0]) | (bitat(p.cwpos[i0 + 1]) << 8) |
-                                (bitat(p.cwpos[i0 + 2]) << 16) | (bitat(p.cwpos[i0 + 3]) << 24);
+                        o4[w] = bitat(p.io.cwpos[i0]) | (bitat(p.io.cwpos[i0 + 1]) << 8) |
+                                (bitat(p.io.cwpos[i0 + 2]) << 16) | (bitat(p.io.cwpos[i0 + 3]) << 24);
                     }
                 } else {
                     for (int i = lane; i < p.N; i += 64) {
-                        const int ci = p.cwpos[i];
-                        p.cw[row * p.N + i] = (uint8_t)((cq[ci >> 5] >> (ci & 31)) & 1u);
+                        const int ci = p.io.cwpos[i];
+                        p.io.cw[row * p.N + i] = (uint8_t)((cq[ci >> 5] >> (ci & 31)) & 1u);
                     }
                 }
             }
-            if (lane == 0) p.metric[row] = rdl_f(pr.R, q);
+            if (lane == 0) p.io.metric[row] = rdl_f(pr.R, q);
         }
-        if (lane == 0) p.count[cw] = nact;
+        if (lane == 0) p.io.count[cw] = nact;
         wsync();
     }
 }

@@ -216,6 +216,32 @@ def test_gpu_tiered_mixed_state_reuse_across_codewords(kdir, monkeypatch):
     assert_same(d.decode(llr), o.decode_batch(llr, 8))
 
 
+# (layers, K, L, split asked) -> (split, lds_bytes, workspace_bytes) of state_info(), read off the
+# library of commit b2bf5e7 on an MI355X (not computed by the code under test). With split=None
+# A^4 x eBCH16^2 at L = 32 does not fit LDS at splits 1 and 2 (the rule's first loop), and it and
+# three other codes then move further layers out for more waves per CU (the second loop).
+B16 = "bch16"
+AUTO_CHOICE = {
+    ((B16, B16, B16), 2048, 8, None): (1, 18864, 122880), ((B16, B16, B16), 2048, 8, 3): (3, 13888, 128000),
+    ((B16, B16, B16), 2048, 16, None): (2, 16752, 238592), ((B16, B16, B16), 2048, 16, 1): (1, 25952, 229376),
+    (("A", B16, B16, B16), 4096, 8, None): (3, 25024, 373248), (("A", B16, B16, B16), 4096, 8, 2): (2, 29632, 368640),
+    (A4EBCH2[0], 2048, 8, None): (4, 20432, 233472), (A4EBCH2[0], 2048, 8, 6): (6, 15456, 238592),
+    (("bch8", "A5", "A", "k4"), 160, 8, None): (1, 4944, 10240), (("bch8", "A5", "A", "k4"), 160, 8, 3): (3, 3296, 12032),
+    (A4EBCH2[0], 2048, 32, None): (5, 23360, 903168), (A4EBCH2[0], 2048, 32, 3): (3, 90880, 835584),
+}
+
+
+@pytest.mark.gpu
+def test_tiered_auto_choice_pinned(kdir):
+    """What split=None chooses, and the layout sizes at it and at one explicit split: creation
+    only, nothing is decoded. grid is left out (it follows the CU count and BCHK_POLAR_WORKSPACE_MB)."""
+    for (layers, K, L, ask), want in AUTO_CHOICE.items():
+        d = tm(any_spec(layers, K, 0, (), seed=1), L, kdir, ask)
+        st = d.state_info()
+        d.close()
+        assert (st["split"], st["lds_bytes"], st["workspace_bytes"]) == want, (layers, L, ask)
+
+
 @pytest.mark.gpu
 def test_gpu_tiered_mixed_all_arikan_cross_check():
     """An all-Arikan code through this kernel: the lists of the Arikan tiered and LDS kernels."""

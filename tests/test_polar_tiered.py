@@ -127,6 +127,31 @@ def test_gpu_tiered_past_the_lds_limit(n, K, L):
     assert_same(tiered(spec, L).decode(llr), o.decode_batch(llr, L))
 
 
+# (n, L, split asked) -> (split, lds_bytes, workspace_bytes) of state_info(), read off the library
+# of commit b2bf5e7 on an MI355X (not computed by the code under test). split=None: at (13, 32)
+# and (14, 32) the first splits do not fit LDS; at (11, 16), (12, 32), (13, 8) and (14, 32) further
+# layers move out for one more wave per CU; at (10, 8) neither loop of the rule acts.
+AUTO_CHOICE = {
+    (10, 8, None): (1, 18192, 18432), (10, 8, 4): (4, 2992, 33792),
+    (11, 16, None): (3, 20032, 125952), (11, 16, 2): (2, 37424, 108544),
+    (12, 32, None): (6, 18144, 564736), (12, 32, 3): (3, 78976, 503808),
+    (13, 8, None): (5, 13104, 278016), (13, 8, 1): (1, 143632, 147456),
+    (13, 32, None): (3, 156800, 1007616), (13, 32, 4): (4, 87200, 1077248),
+    (14, 32, None): (7, 51456, 2276352), (14, 32, 5): (5, 103616, 2224128),
+}
+
+
+@pytest.mark.gpu
+def test_tiered_auto_choice_pinned():
+    """What split=None chooses, and the layout sizes at it and at one explicit split: creation
+    only, nothing is decoded. grid is left out (it follows the CU count and BCHK_POLAR_WORKSPACE_MB)."""
+    for (n, L, ask), want in AUTO_CHOICE.items():
+        d = tiered(arikan_spec(n, 1 << (n - 1)), L, ask)
+        st = d.state_info()
+        d.close()
+        assert (st["split"], st["lds_bytes"], st["workspace_bytes"]) == want, (n, L, ask)
+
+
 LONG = sorted(glob.glob(os.path.join(GOLD, "long_ref_*.txt.gz")))
 
 
