@@ -357,7 +357,10 @@ int bchk_polar_params(const bchk_polar *pc, int *n, int *k, int *unshortened, in
  * batched: llr [B][N] float, log P(0)/P(1) as the decoder reads them (bit 1 when < 0);
  * per codeword the list, best path first: info [B][L][K], cw [B][L][N] (may be NULL),
  * metric [B][L] (path metrics, 0 = the hard decision), count [B] (rows written; rows past
- * it are left as they were). */
+ * it are left as they were). A code of dimension K = 0 is decoded like any other: count 1, the
+ * frozen word and its metric, no information byte written (info must still be non-NULL); only
+ * the entry points that need Eb/N0, and with it the rate -- bchk_polar_generate_device,
+ * bchk_polar_sweep_device, bchk_polar_genie_run, bchk_polar_design_genie -- refuse it. */
 int bchk_polar_decode_host(bchk_polar *pc, const float *llr, size_t B, uint8_t *info,
                            uint8_t *cw, float *metric, int32_t *count);
 int bchk_polar_decode_device(bchk_polar *pc, const float *d_llr, size_t B, uint8_t *d_info,

@@ -147,6 +147,11 @@ POLAR_MIXED = [(("k4", "A"), 4, 0, ()), (("bch8", "A"), 8, 2, ()), (("bch16", "A
 # the GPU decoder's 2^12: that form is pinned by its trellis fixture (trellis_bch32) alone.
 POLAR_MIXED_LISTS = (1, 4, 8)
 POLAR_WORDS = 32
+# shortened codes (the decoder's 100000 at a shortened symbol): tests/test_polar_contract.py's
+# specifications of these names -- A^6 with five shortened symbols, eBCH16 x A with three, A^7
+# shortened, punctured and dynamically frozen -- at 0 dB, where the lists diverge, the upper half
+# of the rows times 4096: with LLRs of order 1 alone no list depends on the mapped value as long as
+# it is the largest (tests/short_codes.py: FIXTURES, with_large_rows)
 
 
 def polar():
@@ -216,6 +221,12 @@ def polar():
         nbits = int(round(np.log2(U)))
         emit(code_fixture("mixed_" + "_".join(layers), spec, [l for l in layers if l != "A"], POLAR_MIXED_LISTS,
                           1.0 + 0.25 * nbits, seed=U + K))
+    import short_codes
+    with tempfile.TemporaryDirectory() as kd:
+        short_codes.write_kernels(kd)
+        for i, name in enumerate(short_codes.FIXTURES):
+            emit(code_fixture("short_" + name, short_codes.short_spec(name, kd), ["bch16"] if "bch16" in name else [],
+                              POLAR_MIXED_LISTS, 0.0, seed=900 + i, llr_map=short_codes.with_large_rows))
     for kname in ("bch8", "bch16", "bch32", "bch32f"):
         l = len(kern[kname])
         rng = np.random.default_rng(l + len(kname))

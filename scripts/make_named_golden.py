@@ -35,7 +35,7 @@ def run_perturbed(args, lines, d):
     return outs[0]
 
 
-def inputs(name, spec, kernels, lists, snr, seed, rows, ties=False, what="named kernels"):
+def inputs(name, spec, kernels, lists, snr, seed, rows, ties=False, what="named kernels", large=None):
     fx = R.Fixture(name, [f"named_ref fixture: code {name} ({what}), Eb/N0 {snr:g} dB, seed {seed}; recorded outputs "
                           "of the reference's vendored decoder and encoder (scripts/make_named_golden.py)"])
     fx.add("spec", [], spec.rstrip("\n").split("\n"))
@@ -53,6 +53,8 @@ def inputs(name, spec, kernels, lists, snr, seed, rows, ties=False, what="named 
     llr = awgn_llr(cw, snr, K / N, seed=seed + 1)
     if ties:  # equal metrics and exact zeros: multiples of 4 (|llr| < 2 becomes 0)
         llr = (4.0 * np.round(llr / 4.0)).astype(np.float32)
+    if large:  # large magnitudes, still below a shortened symbol's 100000
+        llr[rows // 2:] *= np.float32(large)
     fx.add("llr", [], [R.hex_row(r) for r in llr])
     for L in lists:
         fx.add("decode", [L], [])
@@ -113,7 +115,7 @@ def main():
             assert shortened_symbol_is_zero(spec, ex["short"]), name
         kernels = {n[1:]: kern[n] for n in layers if n.startswith("-")}
         snr = 1.0 + 0.25 * np.log2(U)
-        save(record(inputs(name, spec, kernels, lists, snr, seed, NL.ROWS, ties=bool(ex.get("ties")))))
+        save(record(inputs(name, spec, kernels, lists, snr, seed, NL.ROWS, ties=bool(ex.get("ties")), large=ex.get("large"))))
     # G in an outer layer with a list: the matrix form of the code, close metrics dropped
     for i, (name, layers, K, lists) in enumerate(NL.OUTER_CASES):
         for seed in range(700 + 10 * i, 710 + 10 * i):

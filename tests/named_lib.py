@@ -52,6 +52,10 @@ CASES = [
     ("bch8_G", ("-bch8.txt", "G"), 12, (1, 8), {}),
     ("A_A5_A_ties", ("A", "A5", "A"), 10, (8,), {"ties": True}),
     ("A_A_G_ties", ("A", "A", "G"), 6, (8,), {"ties": True}),
+    # u_29, the last input, frozen: symbol 11 is then always 0. G is not the innermost layer, so L = 1
+    # only; the upper half of the LLR rows times 4096, magnitudes that only a mapped value of the
+    # reference's size (100000 at the shortened symbol) still outweighs in every min
+    ("A5_G_A_short", ("A5", "G", "A"), 14, (1,), {"short": (11,), "freeze": (29,), "large": 4096.0}),
 ]
 OUTER_CASES = [("outerG_G_A_A", ("-G.txt", "A", "A"), 9, (4, 8)), ("outerG_A_G_A", ("A", "-G.txt", "A"), 9, (4, 8))]
 

@@ -115,18 +115,20 @@ def pw_order(n):
     return sorted(range(U), key=lambda i: (w[i], i))
 
 
-def arikan_spec(n, K, dyn=0, punct=(), seed=0):
+def arikan_spec(n, K, dyn=0, punct=(), seed=0, short=(), freeze=()):
     """Spec text of a length-2^n Arikan polar code of dimension K: the U - K least reliable
     symbols frozen (`dyn` of them dynamically, each as the XOR of two earlier symbols),
-    `punct` punctured positions (N = U - len(punct))."""
+    `punct` punctured and `short` shortened positions (N = U - len(punct) - len(short)).
+    `freeze` are frozen to 0 whatever their rank, within the U - K (what makes a symbol always 0,
+    so that it can be shortened: see shorten())."""
     U = 1 << n
     rng = np.random.default_rng(seed)
-    frozen = sorted(pw_order(n)[:U - K])
-    dynset = set(rng.choice([f for f in frozen if f >= 2], size=min(dyn, len(frozen)),
+    frozen = sorted(list(freeze) + [i for i in pw_order(n) if i not in freeze][:U - K - len(freeze)])
+    dynset = set(rng.choice([f for f in frozen if f >= 2 and f not in freeze], size=min(dyn, len(frozen)),
                             replace=False).tolist()) if dyn else set()
-    lines = [f"{U - len(punct)} {K} 0 {n} 0 {len(punct)}", " ".join(["A"] * n)]
-    if punct:
-        lines.append(" ".join(str(p) for p in punct))
+    lines = [f"{U - len(punct) - len(short)} {K} 0 {n} {len(short)} {len(punct)}", " ".join(["A"] * n)]
+    if short or punct:
+        lines.append(" ".join(str(p) for p in tuple(short) + tuple(punct)))
     for f in frozen:
         if f in dynset:
             a, b = sorted(rng.choice(f, size=2, replace=False).tolist())
@@ -134,6 +136,31 @@ def arikan_spec(n, K, dyn=0, punct=(), seed=0):
         else:
             lines.append(f"1 {f}")
     return "\n".join(lines) + "\n"
+
+
+def always_zero_symbols(spec, kernel_dir=None):
+    """The symbols of the unshortened codeword that are 0 for every information word: 0 in the
+    encoding of the zero word and of the K unit words (the code is affine in the information
+    bits). `spec` shortens and punctures nothing."""
+    o = PolarOracle(spec, kernel_dir)
+    assert o.N == o.U
+    seen = o.encode_unshortened(np.zeros(o.K, np.uint8))
+    for k in range(o.K):
+        seen |= o.encode_unshortened(np.eye(o.K, dtype=np.uint8)[k])
+    return [int(i) for i in np.flatnonzero(seen == 0)]
+
+
+def shorten(build, U, s, punct=(), kernel_dir=None, zero_form=None):
+    """A valid shortened specification from a builder build(short=, freeze=, punct=) such as
+    arikan_spec: the last s encoder inputs are frozen to 0, and s of the symbols that this makes
+    always 0 are shortened -- the lowest-numbered ones, so not the run at the very end where the
+    kernels leave a choice. zero_form(spec) rewrites the unshortened specification for
+    always_zero_symbols (named kernels in their matrix form, which the oracle takes)."""
+    freeze = tuple(range(U - s, U))
+    plain = build(short=(), freeze=freeze, punct=())
+    zeros = [z for z in always_zero_symbols(zero_form(plain) if zero_form else plain, kernel_dir) if z not in punct]
+    assert len(zeros) >= s, (zeros, s)
+    return build(short=tuple(zeros[:s]), freeze=freeze, punct=tuple(punct))
 
 
 def awgn_llr(cw, snr_db, rate, seed):

@@ -128,24 +128,28 @@ def kdir(tmp_path_factory):
     return str(d)
 
 
-def mixed_spec(layers, K, dyn=0, punct=(), seed=0):
+def mixed_spec(layers, K, dyn=0, punct=(), seed=0, short=(), freeze=()):
     """Spec text over the given layer names ("A" or a kernel file name): the U - K lowest
-    indices frozen except a few swapped for variety, `dyn` of them dynamically frozen."""
+    indices frozen except a few swapped for variety, `dyn` of them dynamically frozen; `punct`
+    punctured and `short` shortened positions; `freeze` frozen to 0 whatever their rank, within
+    the U - K (polar_lib.shorten)."""
     sizes = [2 if name == "A" else len(KERNELS[name]) for name in layers]
     U = int(np.prod(sizes))
     rng = np.random.default_rng(seed)
-    order = list(range(U))
+    order = [i for i in range(U) if i not in freeze]
+    nf = U - K - len(freeze)  # the boundary within `order`
+    lo, hi = max(0, nf - 4), min(len(order), nf + 4)
     for _ in range(U // 8):  # a few swaps near the boundary
-        i = int(rng.integers(max(0, U - K - 4), min(U, U - K + 4)))
-        j = int(rng.integers(max(0, U - K - 4), min(U, U - K + 4)))
+        i = int(rng.integers(lo, hi))
+        j = int(rng.integers(lo, hi))
         order[i], order[j] = order[j], order[i]
-    frozen = sorted(order[:U - K])
-    dynset = set(rng.choice([f for f in frozen if f >= 2], size=min(dyn, len([f for f in frozen if f >= 2])),
-                            replace=False).tolist()) if dyn else set()
+    frozen = sorted(list(freeze) + order[:nf])
+    cand = [f for f in frozen if f >= 2 and f not in freeze]
+    dynset = set(rng.choice(cand, size=min(dyn, len(cand)), replace=False).tolist()) if dyn else set()
     names = ["A" if n == "A" else f"-{n}.txt" for n in layers]
-    lines = [f"{U - len(punct)} {K} 0 {len(layers)} 0 {len(punct)}", " ".join(names)]
-    if punct:
-        lines.append(" ".join(str(p) for p in punct))
+    lines = [f"{U - len(punct) - len(short)} {K} 0 {len(layers)} {len(short)} {len(punct)}", " ".join(names)]
+    if short or punct:
+        lines.append(" ".join(str(p) for p in tuple(short) + tuple(punct)))
     for f in frozen:
         if f in dynset:
             a, b = sorted(rng.choice(f, size=2, replace=False).tolist())

@@ -76,10 +76,11 @@ def test_the_fixture_set_is_the_one_the_generator_writes():
     assert names == sorted([
         "arikan_n3", "arikan_n4", "arikan_n5", "arikan_n6", "arikan_n8", "arikan_n7_ties",
         "mixed_k4_A", "mixed_bch8_A", "mixed_bch16_A", "mixed_bch32f", "mixed_bch32f_A",
+        "short_arikan_n6", "short_bch16_A", "short_arikan_n7",
         "trellis_bch8", "trellis_bch16", "trellis_bch32", "trellis_bch32f"])
     for p in CODE_FILES:
         fx = fixture(p)
-        want = [8] if fx.name.endswith("ties") else [1, 4, 8] if fx.name.startswith("mixed") else [1, 2, 4, 8, 32]
+        want = [8] if fx.name.endswith("ties") else [1, 4, 8] if fx.name.startswith(("mixed", "short")) else [1, 2, 4, 8, 32]
         assert fx.list_sizes == want and 32 <= len(fx.llr) <= 64 and len(fx.info) == 30
 
 
