@@ -227,6 +227,12 @@ def polar():
         for i, name in enumerate(short_codes.FIXTURES):
             emit(code_fixture("short_" + name, short_codes.short_spec(name, kd), ["bch16"] if "bch16" in name else [],
                               POLAR_MIXED_LISTS, 0.0, seed=900 + i, llr_map=short_codes.with_large_rows))
+    # dense dynamic freezing (tests/dense_codes.py): 64, 33 and 40 constraints live at once, the
+    # last code with constraints of 65 and 130 terms
+    import dense_codes
+    for i, name in enumerate(dense_codes.FIXTURES):
+        emit(code_fixture(name, dense_codes.spec(name), [l for l in dense_codes.layers(name) if l != "A"],
+                          POLAR_MIXED_LISTS, dense_codes.SNR[name], seed=2000 + i))
     for kname in ("bch8", "bch16", "bch32", "bch32f"):
         l = len(kern[kname])
         rng = np.random.default_rng(l + len(kname))

@@ -41,7 +41,8 @@ matches_oracle, "rounds" / "items" their two modes):
   rg[1] lv                dead state: every active lane reloads lv after the layer loop, before
                           its first use -- nothing can fail
   rg[2] dm (low word)     every code with dynamic frozen symbols (all but bch64f-32)
-  rg[3] dm (high word)    not covered: needs more than 32 simultaneously active constraints
+  rg[3] dm (high word)    tests/test_polar_dense_dyn.py::test_gpu_dense_tiny_budget_matches_oracle: 34 constraints
+                          live at once (mask bits 32 and 33 in use), L = 4, 8, both modes
   rg[4] rw                every case suspended with information bits pending in the record word
   LDS [0, o_ph)           every case (channel, S, C, O)
   LDS [o_act, o_tm)       act is rebuilt by list_act(active) on resume; rec: 64 bch64f-40 / A-bch64f-64 /

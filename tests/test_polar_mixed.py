@@ -159,6 +159,18 @@ def mixed_spec(layers, K, dyn=0, punct=(), seed=0, short=(), freeze=()):
     return "\n".join(lines) + "\n"
 
 
+def dense_mixed_spec(layers, K, active, pivot, widths=(), seed=0, lo_info=None, late=0):
+    """mixed_spec's twin for dense dynamic freezing (polar_lib.dense_constraints): `active`
+    constraints live across symbol `pivot`, `late` more on reused mask bits. The symbols'
+    rank is a seeded shuffle (no good code); lo_info defaults to half of K."""
+    from polar_lib import dense_constraints
+    U = int(np.prod([2 if name == "A" else len(KERNELS[name]) for name in layers]))
+    rank = np.random.default_rng(seed + 1000).permutation(U).tolist()
+    lines = dense_constraints(U, K, active, pivot, widths, seed, rank, K // 2 if lo_info is None else lo_info, late)
+    names = ["A" if n == "A" else f"-{n}.txt" for n in layers]
+    return "\n".join([f"{U} {K} 0 {len(layers)} 0 0", " ".join(names)] + lines) + "\n"
+
+
 def _same(got, want):
     gc, gi, gw, gm = got
     wc, wi, ww, wm = want

@@ -12,6 +12,9 @@ oracle/make_golden.py polar`. Format: tests/polar_ref_lib.py.
   regeneration: where oracle/_ref/polar_ref exists, re-running it on a fixture's inputs gives
         the fixture byte for byte.
 
+The dyn_* fixtures (tests/dense_codes.py) are codes with 33 to 64 dynamic freezing constraints
+live at once and constraints of 65 and 130 terms: the upper half of the decoders' 64-bit mask.
+
 Not pinned (no fixture can exist): kernels of size >= 64, which the reference's trellis
 processor refuses (TrellisKernelProcessor.cpp:71-72) -- the 64 x 64 ordered-statistics path
 stays checked against the oracle's enumeration properties only (tests/test_polar_ml.py).
@@ -77,10 +80,11 @@ def test_the_fixture_set_is_the_one_the_generator_writes():
         "arikan_n3", "arikan_n4", "arikan_n5", "arikan_n6", "arikan_n8", "arikan_n7_ties",
         "mixed_k4_A", "mixed_bch8_A", "mixed_bch16_A", "mixed_bch32f", "mixed_bch32f_A",
         "short_arikan_n6", "short_bch16_A", "short_arikan_n7",
+        "dyn_arikan_n8_a64", "dyn_arikan_n7_a33", "dyn_A_bch16_bch8_a40",
         "trellis_bch8", "trellis_bch16", "trellis_bch32", "trellis_bch32f"])
     for p in CODE_FILES:
         fx = fixture(p)
-        want = [8] if fx.name.endswith("ties") else [1, 4, 8] if fx.name.startswith(("mixed", "short")) else [1, 2, 4, 8, 32]
+        want = [8] if fx.name.endswith("ties") else [1, 4, 8] if fx.name.startswith(("mixed", "short", "dyn")) else [1, 2, 4, 8, 32]
         assert fx.list_sizes == want and 32 <= len(fx.llr) <= 64 and len(fx.info) == 30
 
 
@@ -102,6 +106,22 @@ def test_fixtures_exercise_what_they_are_for():
     assert fixture(os.path.join(R.GOLD, "polar_ref_arikan_n6.txt.gz")).spec.split("\n")[2] == "1 7"
     assert fixture(os.path.join(R.GOLD, "polar_ref_arikan_n8.txt.gz")).spec.count("\n3 ") == 12
     assert fixture(os.path.join(R.GOLD, "polar_ref_arikan_n5.txt.gz")).spec.count("\n3 ") == 3
+    # dense dynamic freezing: as many constraints live at once as the name says, and every bit of
+    # the mask's upper half that the code uses carries a 1 in some transmitted word -- the frozen
+    # symbol on that bit, the XOR of its listed terms over the fixture's information words
+    import dense_codes
+    from polar_lib import constraint_bits, max_active, spec_inputs
+    assert sorted(dense_codes.FIXTURES) == sorted(_ids(p) for p in CODE_FILES if _ids(p).startswith("dyn"))
+    for name in dense_codes.FIXTURES:
+        fx = fixture(os.path.join(R.GOLD, f"polar_ref_{name}.txt.gz"))
+        assert fx.spec == dense_codes.spec(name)
+        active = dense_codes.claimed_active(name)
+        assert max_active(fx.spec) == active > 32
+        bit = constraint_bits(fx.spec)
+        assert max(bit.values()) == active - 1
+        u = spec_inputs(fx.spec, len(fx.encoded[0]), fx.info)
+        for b in range(32, active):
+            assert any(u[:, f].any() for f, v in bit.items() if v == b), (name, b)
 
 
 def test_fixture_kernels_are_the_products_extended_bch_kernels():
