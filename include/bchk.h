@@ -389,9 +389,10 @@ int bchk_polar_encode_host(const bchk_polar *pc, const uint8_t *info, size_t B, 
 int bchk_polar_sync(bchk_polar *pc);
 void *bchk_polar_stream(bchk_polar *pc);
 
-/* ---- Polar FER simulation on the device: the AWGN/BPSK part of the vendored simulator's
- * iteration (out/external/Simulator.cpp:104-110, :139-335, headers/external/Modem.h:64-78) as
- * kernels (csrc/polar_channel.hip). Device pointers; each call enqueues on `stream` (NULL =
+/* ---- Polar FER simulation on the device: the BPSK part of the vendored simulator's
+ * iteration (out/external/Simulator.cpp:104-114, :139-335, headers/external/Modem.h:64-78) as
+ * kernels (csrc/polar_channel.hip), over AWGN and, through the *_channel* entry points, real
+ * Rayleigh fading with ideal channel knowledge and the BSC (Simulator.cpp:179-191). Device pointers; each call enqueues on `stream` (NULL =
  * the context's stream); B = 0 is a no-op; B > 2^32 - 1 is BCHK_EINVAL. */
 /* CMixedKernelEncoder::Encode (MixedKernelEncoder.cpp:142-177) as a kernel, bit for bit
  * bchk_polar_encode_host for every code bchk_polar_create accepts: d_info [B][K] -> d_cw [B][N]. */
@@ -407,6 +408,38 @@ int bchk_polar_encode_device(bchk_polar *pc, const uint8_t *d_info, size_t B, ui
  * GSL mt19937 stream bit for bit (the same caveat as bchk_generate_device). */
 int bchk_polar_generate_device(bchk_polar *pc, double snr_db, size_t B, uint64_t seed, uint64_t word0,
                                uint8_t *d_info, uint8_t *d_cw, float *d_llr, void *stream);
+/* The channels of the simulator's loop (Simulator.cpp:179-191). The entry points without a
+ * channel argument mean BCHK_CHANNEL_AWGN. */
+#define BCHK_CHANNEL_AWGN 0     /* y = x + sigma z; param = Eb/N0 in dB                          */
+#define BCHK_CHANNEL_RAYLEIGH 1 /* y = h x + sigma z, h known to the receiver; param = the       */
+                                /* average Eb/N0 in dB                                           */
+#define BCHK_CHANNEL_BSC 2      /* y = +-x; param = the crossover probability p, 0 < p <= 0.5    */
+/* bchk_polar_generate_device over any of the three channels. The stream is the same: for a given
+ * (seed, word0) d_info and d_cw are byte for byte those of bchk_polar_generate_device whatever
+ * the channel, x is BPSK with bit 1 -> +1 (Modem.h:64) and z the Gaussian of flat element
+ * G = w N + position. The Rayleigh channel and the BSC draw one more uniform per element:
+ *   u(G) = (a 2^21 + (b >> 11) + 1) 2^-53 in (0, 1], (a, b) = output words (0, 1) when G is even
+ *   and (2, 3) when G is odd of the Philox4x32-10 call with counter (G / 2 low, G / 2 high,
+ *   0xFAD1, 0) under the key (seed low, seed high).
+ * BCHK_CHANNEL_AWGN: bchk_polar_generate_device bit for bit.
+ * BCHK_CHANNEL_RAYLEIGH (Simulator.cpp:183-187, SimpleChannels.h:139): h = sqrt(-log u), the
+ *   gsl_ran_rayleigh draw of scale 1 / sqrt 2, so E[h^2] = 1; y = h x + sigma z in double, sigma
+ *   as for AWGN at the same Eb/N0 (Simulator.cpp:108: with E[h^2] = 1 the average Eb/N0);
+ *   LLR = (float)(-2 h y / sigma^2), evaluated as ((-2 h) y) / sigma^2 (Modem.h:78 with the
+ *   fading factor).
+ * BCHK_CHANNEL_BSC (Simulator.cpp:188-191, :114): y = x where u > p, -x where u <= p;
+ *   LLR = (float)(-2 y) = +-2, the reference's noise variance 1 -- not log((1 - p) / p): the
+ *   decoder is min-sum, its decisions do not depend on the scale. Counter [6] of
+ *   bchk_polar_count_device then counts the flips.
+ * d_h [B][N] and d_y [B][N], doubles, may each be NULL and are written only when given: the
+ * fading factor h (Rayleigh only) and the channel output y ahead of the demodulator. One
+ * launch, as before. BCHK_EINVAL before any device call, the message naming the argument: an
+ * unknown channel; p outside (0, 0.5] or NaN; d_h given for AWGN or the BSC; K = 0 (as
+ * bchk_polar_generate_device: the code has no rate). The BEC (commented out at
+ * Simulator.cpp:193), block or correlated fading and higher-order modems are not built. */
+int bchk_polar_generate_channel_device(bchk_polar *pc, int channel, double param, size_t B, uint64_t seed,
+                                       uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h,
+                                       double *d_y, void *stream);
 /* The counters of CSimulator::Iterate (Simulator.cpp:201-318) for one decoded batch -- sent
  * d_info_tx [B][K], d_cw_tx [B][N], the channel's d_llr [B][N], and bchk_polar_decode_device's
  * d_info [B][L][K], d_cw [B][L][N] (required: the counters need the codeword rows), d_count
@@ -443,6 +476,15 @@ typedef struct bchk_polar_point {
 int bchk_polar_sweep_device(bchk_polar *pc, double snr_from, double snr_step, int points, uint64_t max_words,
                             uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
                             double *seconds, uint64_t *words_decoded);
+/* The same loop over `channel` (bchk_polar_generate_channel_device): the points are Eb/N0 values
+ * in dB for AWGN and Rayleigh and crossover probabilities p for the BSC (the record's snr_db
+ * field then holds p), from + i step. The same exact cut in word order, the word index running
+ * on across points. Every point's parameter is checked before any work (BCHK_EINVAL for an
+ * unknown channel or a p outside (0, 0.5]); BCHK_CHANNEL_AWGN gives bchk_polar_sweep_device's
+ * records exactly. */
+int bchk_polar_sweep_channel_device(bchk_polar *pc, int channel, double from, double step, int points,
+                                    uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                    bchk_polar_point *out, double *seconds, uint64_t *words_decoded);
 
 /* ---- BCH polar-kernel construction and the column-permutation search (root bchCoder.cpp;
  * csrc/kernel_search.hip). Kernels are row-major l x l bytes (0/1). */
@@ -590,6 +632,17 @@ int bchk_polar_genie_run(bchk_polar *pc, double snr_db, uint64_t words, uint64_t
 int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words,
                             uint64_t seed, int device, uint64_t *err, int64_t *soft, char *spec, size_t spec_len,
                             size_t *needed);
+/* bchk_polar_genie_run and bchk_polar_design_genie with (channel, param) of
+ * bchk_polar_generate_channel_device in place of snr_db: nothing in the genie-aided statistics is
+ * specific to AWGN, only the source of the LLRs is, and a frozen set designed this way is a
+ * design for the channel the decoder will see (for the BSC at crossover probability param). The
+ * same refusals, and BCHK_EINVAL for an unknown channel or a p outside (0, 0.5], checked first;
+ * BCHK_CHANNEL_AWGN gives the calls above exactly. */
+int bchk_polar_genie_run_channel(bchk_polar *pc, int channel, double param, uint64_t words, uint64_t seed,
+                                 uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds);
+int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K, int channel, double param,
+                                    uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
+                                    char *spec, size_t spec_len, size_t *needed);
 
 const char *bchk_last_error(void);
 const char *bchk_version(void);

@@ -46,10 +46,15 @@ EXPORTS = (
     "bchk_kernel_column_search",
     "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
     "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_polar_genie_device", "bchk_polar_genie_run",
-    "bchk_polar_design_genie", "bchk_last_error", "bchk_version",
+    "bchk_polar_design_genie", "bchk_polar_generate_channel_device", "bchk_polar_sweep_channel_device",
+    "bchk_polar_genie_run_channel", "bchk_polar_design_genie_channel", "bchk_last_error", "bchk_version",
 )
 
-# struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device
+# BCHK_CHANNEL_*: the channels of the polar simulation front-end
+CHANNEL_AWGN, CHANNEL_RAYLEIGH, CHANNEL_BSC = 0, 1, 2
+CHANNELS = {"awgn": CHANNEL_AWGN, "rayleigh": CHANNEL_RAYLEIGH, "bsc": CHANNEL_BSC}
+
+# struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device (on the BSC snr_db holds p)
 POLAR_POINT_DTYPE = np.dtype([("snr_db", "<f8"), ("c", "<u8", (8,))])
 POLAR_COUNTERS = ("words", "block_errors", "info_bit_errors", "code_bit_errors", "ml_errors", "list_errors",
                   "raw_bit_errors", "no_decision")
@@ -171,6 +176,12 @@ def lib():
     L.bchk_polar_genie_run.argtypes = [vp, dbl, u64, u64, u64, sz, vp, vp, C.POINTER(dbl)]
     L.bchk_polar_design_genie.argtypes = [C.c_char_p, C.c_char_p, i32, dbl, u64, u64, i32, vp, vp, C.c_char_p, sz,
                                           C.POINTER(sz)]
+    L.bchk_polar_generate_channel_device.argtypes = [vp, i32, dbl, sz, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.bchk_polar_sweep_channel_device.argtypes = [vp, i32, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
+                                                  C.POINTER(u64)]
+    L.bchk_polar_genie_run_channel.argtypes = [vp, i32, dbl, u64, u64, u64, sz, vp, vp, C.POINTER(dbl)]
+    L.bchk_polar_design_genie_channel.argtypes = [C.c_char_p, C.c_char_p, i32, i32, dbl, u64, u64, i32, vp, vp,
+                                                  C.c_char_p, sz, C.POINTER(sz)]
     L.bchk_last_error.restype = C.c_char_p
     L.bchk_version.restype = C.c_char_p
     _lib = L
@@ -184,6 +195,14 @@ def _check(rc):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _channel(channel):
+    """BCHK_CHANNEL_* of "awgn" | "rayleigh" | "bsc"."""
+    try:
+        return CHANNELS[channel]
+    except (KeyError, TypeError):
+        raise ValueError(f"channel must be one of {sorted(CHANNELS)}, not {channel!r}") from None
 
 
 class KanekoKernelProcessor:
@@ -418,8 +437,9 @@ class KanekoKernelProcessor:
 class PolarListDecoder:
     """CMixedKernelListDecoder(Spec, ListSize) + Decode (out/external/MixedKernelListDecoder.cpp
     :9, :211-268) on the GPU: batched SC-list decoding of a polar code given by the
-    reference's specification text, and the AWGN/BPSK simulation around it (encode_device,
-    generate_device, count_device, sweep_device: out/external/Simulator.cpp). Layers: "A"
+    reference's specification text, and the BPSK simulation around it over AWGN, Rayleigh fading
+    and the BSC (encode_device, generate_device, count_device, sweep_device:
+    out/external/Simulator.cpp). Layers: "A"
     (Arikan), matrix files ("-file"), and the library's named kernels "G" (3 x 3) and "A5"
     (5 x 5, rows as CA5Kernel::Multiply computes them), in any case, decoded by their own f/g
     processors with the state carried per path: code lengths such as 12, 24, 40, 60, 96. With
@@ -508,11 +528,17 @@ class PolarListDecoder:
         """The encoder on the GPU: d_info [B][K] u8 -> d_cw [B][N] u8 (device pointers)."""
         _check(lib().bchk_polar_encode_device(self._h, d_info or None, B, d_cw or None, stream))
 
-    def generate_device(self, snr_db, B, d_llr, d_info=None, d_cw=None, seed=1, word0=0, stream=None):
+    def generate_device(self, snr_db, B, d_llr, d_info=None, d_cw=None, seed=1, word0=0, stream=None,
+                        channel="awgn", d_h=None, d_y=None):
         """On-GPU channel: words [word0, word0 + B) of the counter-based stream at Eb/N0 snr_db into
-        d_llr [B][N] f32 and, where given, d_info [B][K] and d_cw [B][N]."""
-        _check(lib().bchk_polar_generate_device(self._h, snr_db, B, seed, word0, d_info or None, d_cw or None,
-                                                d_llr or None, stream))
+        d_llr [B][N] f32 and, where given, d_info [B][K] and d_cw [B][N]. channel = "awgn",
+        "rayleigh" (real Rayleigh fading known to the receiver, snr_db the average Eb/N0) or "bsc"
+        (snr_db is then the crossover probability p, LLRs +-2); information bits and codewords do
+        not depend on it. d_h and d_y [B][N] f64, where given, receive the fading factor (Rayleigh
+        only) and the channel output."""
+        _check(lib().bchk_polar_generate_channel_device(self._h, _channel(channel), snr_db, B, seed, word0,
+                                                        d_info or None, d_cw or None, d_llr or None, d_h or None,
+                                                        d_y or None, stream))
 
     def count_device(self, d_info_tx, d_cw_tx, d_llr, d_info, d_cw, d_count, B, d_out8, d_flags=None,
                      stream=None):
@@ -522,15 +548,17 @@ class PolarListDecoder:
                                              d_info or None, d_cw or None, d_count or None, B, d_out8 or None,
                                              d_flags or None, stream))
 
-    def sweep_device(self, snr_from, snr_step, points, max_words, max_errors, seed=1, batch=0):
+    def sweep_device(self, snr_from, snr_step, points, max_words, max_errors, seed=1, batch=0, channel="awgn"):
         """The FER simulation end to end on the GPU: ([(snr_db, counters [8] ints)], seconds,
         words decoded). Each point runs until max_words words or max_errors block errors, cut
-        exactly in word order; the word index runs on across points."""
+        exactly in word order; the word index runs on across points. channel as for
+        generate_device; on "bsc" the points are crossover probabilities."""
         out = np.zeros(max(points, 0), POLAR_POINT_DTYPE)
         secs, words = C.c_double(0.0), C.c_uint64(0)
-        _check(lib().bchk_polar_sweep_device(self._h, snr_from, snr_step, points, max_words, max_errors, seed,
-                                             batch, _p(out) if points > 0 else None, C.byref(secs),
-                                             C.byref(words)))
+        _check(lib().bchk_polar_sweep_channel_device(self._h, _channel(channel), snr_from, snr_step, points,
+                                                     max_words, max_errors, seed, batch,
+                                                     _p(out) if points > 0 else None, C.byref(secs),
+                                                     C.byref(words)))
         return [(float(r["snr_db"]), [int(v) for v in r["c"]]) for r in out], secs.value, words.value
 
     def genie_device(self, d_info_tx, d_llr, B, d_err, d_soft, d_dec_llr=None, d_u=None, stream=None):
@@ -541,14 +569,15 @@ class PolarListDecoder:
         _check(lib().bchk_polar_genie_device(self._h, d_info_tx or None, d_llr or None, B, d_err or None,
                                              d_soft or None, d_dec_llr or None, d_u or None, stream))
 
-    def genie_run(self, snr_db, words, seed=1, word0=0, batch=0):
+    def genie_run(self, snr_db, words, seed=1, word0=0, batch=0, channel="awgn"):
         """Words [word0, word0 + words) of generate_device's stream through genie_device:
-        (err [U] u64, soft [U] i64, seconds), a function of (code, snr_db, seed, word0, words)."""
+        (err [U] u64, soft [U] i64, seconds), a function of (code, channel, snr_db, seed, word0,
+        words). channel as for generate_device."""
         err = np.zeros(self.U, np.uint64)
         soft = np.zeros(self.U, np.int64)
         secs = C.c_double(0.0)
-        _check(lib().bchk_polar_genie_run(self._h, snr_db, words, seed, word0, batch, _p(err), _p(soft),
-                                          C.byref(secs)))
+        _check(lib().bchk_polar_genie_run_channel(self._h, _channel(channel), snr_db, words, seed, word0, batch,
+                                                  _p(err), _p(soft), C.byref(secs)))
         return err, soft, secs.value
 
     def sync(self):
@@ -753,18 +782,20 @@ def design_bec(layers, K, capacity=0.5, kernel_dir=None, samples=1 << 16, seed=1
     return spec, cap[:int(spec.split()[0])].copy()
 
 
-def design_genie(layers, K, snr_db, words, kernel_dir=None, seed=1, device=0):
-    """Monte-Carlo AWGN design over the kernels of `layers`: the symbols ranked by their genie-aided
+def design_genie(layers, K, snr_db, words, kernel_dir=None, seed=1, device=0, channel="awgn"):
+    """Monte-Carlo design over the kernels of `layers`: the symbols ranked by their genie-aided
     error counts over `words` words of the stream `seed` at Eb/N0 snr_db (ties: the larger soft sum,
     then the higher index) -> (spec text for PolarListDecoder, err [U] u64, soft [U] i64).
-    Layers may be "A", matrix files, and the named kernels "G" and "A5"."""
+    Layers may be "A", matrix files, and the named kernels "G" and "A5". channel = "awgn",
+    "rayleigh" or "bsc" (snr_db is then the crossover probability): the design is for that channel."""
     line = layers if isinstance(layers, str) else " ".join(layers)
     err = np.zeros(16384, np.uint64)
     soft = np.zeros(16384, np.int64)
     buf = C.create_string_buffer(64 + len(line) + 8 * 16384)
     needed = C.c_size_t()
-    _check(lib().bchk_polar_design_genie(line.encode(), kernel_dir.encode() if kernel_dir else None, K, snr_db, words,
-                                         seed, device, _p(err), _p(soft), buf, len(buf), C.byref(needed)))
+    _check(lib().bchk_polar_design_genie_channel(line.encode(), kernel_dir.encode() if kernel_dir else None, K,
+                                                 _channel(channel), snr_db, words, seed, device, _p(err), _p(soft),
+                                                 buf, len(buf), C.byref(needed)))
     spec = buf.value.decode()
     U = int(spec.split()[0])
     return spec, err[:U].copy(), soft[:U].copy()

@@ -13,8 +13,15 @@
 //   noise of flat element G = w * n + position: element G & 1 of the Box-Muller pair of counter
 //                                               (G / 2 low, G / 2 high, 0x5EED, 0): u1 from
 //                                               output words (0, 1), u2 from (2, 3)
+//   fading / crossover uniform u(G) of the same flat element G (polar stream, Rayleigh and BSC
+//   channels):                                  counter (G / 2 low, G / 2 high, 0xFAD1, 0);
+//                                               u = unit53 of output words (0, 1) when G is
+//                                               even, of (2, 3) when G is odd: (a 2^21 + (b >> 11)
+//                                               + 1) 2^-53 in (0, 1] for the word pair (a, b)
 //   BEC pattern draw of sample s, weight w:     (s low, s high, w, 0xBEC00000 + attempt)
-// tests/philox_lib.py restates all of it; tests/test_stream_reference.py compares.
+// Word 2 tells the four apart: 0xFFFFFFFF, 0x5EED, 0xFAD1, and a weight of at most 64.
+// tests/philox_lib.py restates all of it but u(G), which tests/channel_lib.py restates;
+// tests/test_stream_reference.py and tests/test_polar_channels.py compare.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,6 +61,13 @@ __device__ __forceinline__ void normal_pair(uint64_t pair, uint32_t k0, uint32_t
     sincospi(2.0 * u2, &sn, &cs);
     z[0] = rad * cs;
     z[1] = rad * sn;
+}
+
+// the fading / crossover uniforms of counter `pair` (elements 2 pair and 2 pair + 1)
+__device__ __forceinline__ void unit_pair(uint64_t pair, uint32_t k0, uint32_t k1, double u[2]) {
+    const U4 r = philox(U4{(uint32_t)pair, (uint32_t)(pair >> 32), 0xFAD1u, 0u}, k0, k1);
+    u[0] = unit53(r.x, r.y);
+    u[1] = unit53(r.z, r.w);
 }
 
 }  // namespace bchk

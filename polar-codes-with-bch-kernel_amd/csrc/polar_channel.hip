@@ -1,10 +1,12 @@
-// polar_channel.hip -- the simulation front-end of the polar SC-list decoder: the AWGN/BPSK
-// part of the vendored simulator's iteration (out/external/Simulator.cpp:104-110, :139-335,
-// headers/external/Modem.h:64-78) as batched kernels, so that a FER experiment never leaves
-// the device. The words are statistically the simulator's (uniform information bits, Gaussian
-// noise of its standard deviation), drawn from the counter-based generator of bchk_philox.h
-// instead of its sequential GSL stream: word w of a (seed, Eb/N0) stream depends only on
-// (seed, w).
+// polar_channel.hip -- the simulation front-end of the polar SC-list decoder: the BPSK part of
+// the vendored simulator's iteration (out/external/Simulator.cpp:104-114, :139-335,
+// headers/external/Modem.h:64-78) over its three channels (:179-191: AWGN, real Rayleigh
+// fading with ideal channel knowledge, the BSC) as batched kernels, so that a FER experiment
+// never leaves the device. The words are statistically the simulator's (uniform information
+// bits, Gaussian noise of its standard deviation, its Rayleigh factor, its flips), drawn from
+// the counter-based generator of bchk_philox.h instead of its sequential GSL stream: word w of
+// a (seed, channel parameter) stream depends only on (seed, w), and the information bits, the
+// codeword and the Gaussian z of an element are the same on every channel.
 //
 // polar_gen_kernel: one wave per word, u as packed bits in LDS. CMixedKernelEncoder::Encode
 // (out/external/MixedKernelEncoder.cpp:142-177): the information bits go to the unfrozen
@@ -15,7 +17,10 @@
 // within a dword below 32, whole dwords above); any other layer is the l x l GF(2) product
 // per block against the krows masks, 64 output symbols per ballot into the second buffer.
 // The transmitted symbols are then stored as bytes, and (generate) element G = word * N +
-// position of the stream takes one of the Box-Muller pair of counter G / 2.
+// position of the stream takes one of the Box-Muller pair of counter G / 2. The kernel is a
+// template over the channel: the Rayleigh and BSC instantiations draw one more uniform per
+// element (the pair of counter G / 2 under the tag 0xFAD1) in the same loop, and every
+// instantiation stores one LLR per symbol, h and y as doubles beside it when asked.
 //
 // polar_count_kernel: one wave per decoded word, CSimulator::Iterate's counters
 // (Simulator.cpp:201-318); CurCorr and MLCorr of an errored word are summed in double in
@@ -33,6 +38,7 @@ namespace {
 using penc::ubit;
 using plist::wsync;
 
+template <int CH>
 __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGenParams p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t psm[];
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -105,7 +111,8 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
             wsync();
             stride = next;
         }
-        // ---- the transmitted symbols, and LLR = -2 y / var of y = BPSK + sigma z
+        // ---- the transmitted symbols, and LLR = -2 y / var of y = BPSK + sigma z (AWGN); the
+        // other channels: Simulator.cpp:183-191
         const uint32_t *c32 = reinterpret_cast<const uint32_t *>(src);
         if (p.cw) {
             uint8_t *cw = p.cw + w * (uint64_t)N;
@@ -113,20 +120,37 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
         }
         if (p.gen) {
             // global element G = word * N + position; the Box-Muller pair of counter G / 2 gives
-            // elements 2 p and 2 p + 1 (a pair may straddle two words: each wave computes it)
+            // elements 2 p and 2 p + 1 (a pair may straddle two words: each wave computes it),
+            // and so does the pair of fading / crossover uniforms
             float *llr = p.llr + w * (uint64_t)N;
+            double *fout = CH == kPolarChanRayleigh && p.fade ? p.fade + w * (uint64_t)N : nullptr;
+            double *yout = p.y ? p.y + w * (uint64_t)N : nullptr;
             const uint64_t ebase = word * (uint64_t)N;
             const uint64_t p0 = ebase >> 1, pend = (ebase + (uint64_t)N + 1) >> 1;
             for (uint64_t pr = p0 + (uint64_t)lane; pr < pend; pr += 64) {
-                double z[2];
-                normal_pair(pr, p.seed_lo, p.seed_hi, z);
+                double z[2], u[2];
+                if (CH != kPolarChanBsc) normal_pair(pr, p.seed_lo, p.seed_hi, z);
+                if (CH != kPolarChanAwgn) unit_pair(pr, p.seed_lo, p.seed_hi, u);
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const int64_t el = (int64_t)(2 * pr + (uint64_t)h) - (int64_t)ebase;  // within the word
                     if (el < 0 || el >= (int64_t)N) continue;
                     const double x = ubit(c32, t.cwpos[el]) ? 1.0 : -1.0;  // Modem.h:64
-                    const double y = x + p.sigma * z[h];
-                    llr[el] = (float)(-2.0 * y / p.var);  // Modem.h:78
+                    if constexpr (CH == kPolarChanAwgn) {
+                        const double y = x + p.sigma * z[h];
+                        llr[el] = (float)(-2.0 * y / p.var);  // Modem.h:78
+                        if (yout) yout[el] = y;
+                    } else if constexpr (CH == kPolarChanRayleigh) {
+                        const double fade = sqrt(-log(u[h]));  // gsl_ran_rayleigh(1 / sqrt 2), Simulator.cpp:184
+                        const double y = fade * x + p.sigma * z[h];  // :185-186
+                        llr[el] = (float)(-2.0 * fade * y / p.var);  // Modem.h:78 with the fading factor
+                        if (fout) fout[el] = fade;
+                        if (yout) yout[el] = y;
+                    } else {
+                        const double y = u[h] > p.cross ? x : -x;  // :189-190
+                        llr[el] = (float)(-2.0 * y);  // noise variance 1 (:114)
+                        if (yout) yout[el] = y;
+                    }
                 }
             }
         }
@@ -229,7 +253,13 @@ int chan_grid(uint32_t B) {
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s) {
     if (p.B == 0) return hipSuccess;
     const size_t lds = (size_t)kPolarChanWaves * polar_gen_wave_bytes(p.t.U, p.t.K);  // <= 25 KiB at U = K = 16384
-    hipLaunchKernelGGL(polar_gen_kernel, dim3(chan_grid(p.B)), dim3(64 * kPolarChanWaves), lds, s, p);
+    const dim3 grid(chan_grid(p.B)), block(64 * kPolarChanWaves);
+    if (p.gen && p.channel == kPolarChanRayleigh)
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanRayleigh>, grid, block, lds, s, p);
+    else if (p.gen && p.channel == kPolarChanBsc)
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanBsc>, grid, block, lds, s, p);
+    else  // AWGN, and every encode
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanAwgn>, grid, block, lds, s, p);
     return hipGetLastError();
 }
 

@@ -2,9 +2,10 @@
 // the bchk_kernel_bec_capacity / bchk_kernel_write_file / bchk_polar_design_bec block): the
 // capacity evaluation of a kernel's BEC polarisation table, the kernel-file writer that stores
 // that table where the reference reads it, and the layer-by-layer capacity recursion that
-// picks the frozen set of a code specification. Also the Monte-Carlo AWGN design
-// (bchk_polar_design_genie): the frozen set ranked by the genie-aided error statistics of
-// bchk_polar_genie_run (polar_host.cpp, polar_genie.hip).
+// picks the frozen set of a code specification. Also the Monte-Carlo design over a simulated
+// channel (bchk_polar_design_genie, bchk_polar_design_genie_channel): the frozen set ranked by
+// the genie-aided error statistics of bchk_polar_genie_run_channel (polar_host.cpp,
+// polar_genie.hip).
 //
 // Reference: CBECCapacityEvaluator (out/external/CapacityEvaluator.cpp:100-140: the table's
 // file layout and GetSubchannelCapacity's Horner rule), CArikanKernel::GetSubchannelCapacity
@@ -30,6 +31,7 @@
 
 namespace bchk {
 void set_last_error(const char *msg);  // bchk_host.cpp
+int polar_check_channel(int channel, double param);  // polar_host.cpp
 }
 
 namespace {
@@ -306,13 +308,16 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
     return BCHK_OK;
 }
 
-// Monte-Carlo AWGN design: the symbols ranked by their genie-aided error statistics
-// (bchk_polar_genie_run) over `words` words of the stream `seed` at snr_db, decoded as the code
-// with the lowest indices frozen (the rate K / U fixes the noise deviation; the statistics do
-// not depend on the frozen set, every earlier symbol being fed back true).
-int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words, uint64_t seed,
-                            int device, uint64_t *err, int64_t *soft, char *spec, size_t spec_len, size_t *needed) {
+// Monte-Carlo design: the symbols ranked by their genie-aided error statistics
+// (bchk_polar_genie_run_channel) over `words` words of the stream `seed` over `channel` at
+// `param`, decoded as the code with the lowest indices frozen (the rate K / U fixes the noise
+// deviation; the statistics do not depend on the frozen set, every earlier symbol being fed
+// back true).
+int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K, int channel, double param,
+                                    uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
+                                    char *spec, size_t spec_len, size_t *needed) {
     if (needed) *needed = 0;
+    if (int rc = bchk::polar_check_channel(channel, param)) return rc;
     if (!layers || !needed) return dfail(BCHK_EINVAL, "NULL argument");
     if (words == 0 || words > (1ull << 31)) return dfail(BCHK_EINVAL, "words must be 1..2^31");
     std::istringstream in(layers);
@@ -349,7 +354,7 @@ int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double 
     if (int rc = bchk_polar_create_kdir(base.c_str(), kdir, 1, device, &pc)) return rc;
     std::vector<uint64_t> e(U);
     std::vector<int64_t> s(U);
-    const int rc = bchk_polar_genie_run(pc, snr_db, words, seed, 0, 0, e.data(), s.data(), nullptr);
+    const int rc = bchk_polar_genie_run_channel(pc, channel, param, words, seed, 0, 0, e.data(), s.data(), nullptr);
     bchk_polar_destroy(pc);
     if (rc) return rc;
     // i is better than j: fewer errors, then the larger soft sum, then the higher index
@@ -370,6 +375,12 @@ int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double 
     if (err) std::copy(e.begin(), e.end(), err);
     if (soft) std::copy(s.begin(), s.end(), soft);
     return BCHK_OK;
+}
+
+int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words, uint64_t seed,
+                            int device, uint64_t *err, int64_t *soft, char *spec, size_t spec_len, size_t *needed) {
+    return bchk_polar_design_genie_channel(layers, kdir, K, BCHK_CHANNEL_AWGN, snr_db, words, seed, device, err, soft,
+                                           spec, spec_len, needed);
 }
 
 }  // extern "C"

@@ -199,7 +199,10 @@ struct PolarEncTables {
 };
 // One launch over B words: an encode (info_in -> cw) or, with gen set, words
 // [word0, word0 + B) of the counter-based stream (bchk_philox.h): information bits, codeword,
-// LLR = (float)(-2 y / var), y = BPSK(bit 1 -> +1) + sigma z in double.
+// LLR = (float)(-2 y / var), y = BPSK(bit 1 -> +1) + sigma z in double. The channel
+// (BCHK_CHANNEL_*, include/bchk.h) chooses the kernel's instantiation: Rayleigh fades x by
+// h = sqrt(-log u) and weighs the LLR with it, the BSC flips x where u <= cross and stores -2 y.
+constexpr int kPolarChanAwgn = 0, kPolarChanRayleigh = 1, kPolarChanBsc = 2;
 struct PolarGenParams {
     PolarEncTables t;
     const uint8_t *info_in;  // [B][K] (encode)
@@ -211,6 +214,10 @@ struct PolarGenParams {
     uint32_t seed_lo, seed_hi;
     int32_t gen;
     double sigma, var;
+    int32_t channel;         // kPolarChan*
+    double cross;            // the BSC's crossover probability
+    double *fade;            // [B][N] h (Rayleigh; may be null)
+    double *y;               // [B][N] the channel output before the demodulator (may be null)
 };
 // CSimulator::Iterate's counters of one decoded batch (Simulator.cpp:201-318), added into
 // out8: words, block errors, information bit errors, code bit errors, ML errors, list errors,

@@ -4,8 +4,9 @@
 // and Decode(pLLR, pInfVectorList, pCodewordList) (headers/external/MixedKernelListDecoder.h:
 // 27-39, out/external/MixedKernelListDecoder.cpp:9, :211-268) and CMixedKernelEncoder::Encode
 // (out/external/MixedKernelEncoder.cpp:142-177). All decoding runs on the GPU. Also the
-// simulation front-end (polar_channel.hip): encode, AWGN words, the simulator's counters and
-// the Eb/N0 sweep of CSimulator (out/external/Simulator.cpp:104-110, :139-335), and the
+// simulation front-end (polar_channel.hip): encode, words over AWGN, Rayleigh fading or the BSC,
+// the simulator's counters and the sweep of CSimulator (out/external/Simulator.cpp:104-114,
+// :139-335, channels :179-191), and the
 // genie-aided SC runs (polar_genie.hip) behind bchk_polar_genie_device / bchk_polar_genie_run.
 #include <hip/hip_runtime.h>
 
@@ -46,6 +47,7 @@ hipError_t launch_polar_genie_sum(const float *dec_llr, const uint8_t *u, uint32
                                   int64_t *soft, hipStream_t s);
 const void *polar_genie_kernel_ptr();
 void set_last_error(const char *msg);  // bchk_host.cpp: the message bchk_last_error returns
+int polar_check_channel(int channel, double param);  // below; polar_design.cpp calls it too
 }  // namespace bchk
 
 namespace {
@@ -998,7 +1000,24 @@ size_t cut_at_error(const std::vector<uint8_t> &flags, size_t nb, uint64_t need)
     return nb;
 }
 
+static_assert(BCHK_CHANNEL_AWGN == kPolarChanAwgn && BCHK_CHANNEL_RAYLEIGH == kPolarChanRayleigh &&
+                  BCHK_CHANNEL_BSC == kPolarChanBsc, "the kernel's channel ids are the ABI's");
+
 }  // namespace
+
+namespace bchk {
+
+// (channel, param) of the bchk_polar_*_channel* entry points (polar_design.cpp too), checked
+// before anything else of a call.
+int polar_check_channel(int channel, double param) {
+    if (channel != BCHK_CHANNEL_AWGN && channel != BCHK_CHANNEL_RAYLEIGH && channel != BCHK_CHANNEL_BSC)
+        return pfail(BCHK_EINVAL, "channel %d unknown (BCHK_CHANNEL_AWGN, _RAYLEIGH or _BSC)", channel);
+    if (channel == BCHK_CHANNEL_BSC && !(param > 0.0 && param <= 0.5))  // NaN fails both
+        return pfail(BCHK_EINVAL, "p = %g: the BSC's crossover probability lies in (0, 0.5]", param);
+    return 0;
+}
+
+}  // namespace bchk
 
 extern "C" {
 
@@ -1017,10 +1036,15 @@ int bchk_polar_encode_device(bchk_polar *c, const uint8_t *d_info, size_t B, uin
     return 0;
 }
 
-// Words [word0, word0 + B) of the counter-based stream `seed` at Eb/N0 snr_db: the noise
-// deviation of CSimulator::SetEbN0 (Simulator.cpp:108, N the transmitted length).
-int bchk_polar_generate_device(bchk_polar *c, double snr_db, size_t B, uint64_t seed, uint64_t word0,
-                               uint8_t *d_info, uint8_t *d_cw, float *d_llr, void *stream) {
+// Words [word0, word0 + B) of the counter-based stream `seed` over `channel`. AWGN and Rayleigh:
+// param = Eb/N0 in dB, the noise deviation of CSimulator::SetEbN0 (Simulator.cpp:108, N the
+// transmitted length). BSC: param = the crossover probability, noise variance 1 (:114).
+int bchk_polar_generate_channel_device(bchk_polar *c, int channel, double param, size_t B, uint64_t seed,
+                                       uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h,
+                                       double *d_y, void *stream) {
+    if (int rc = polar_check_channel(channel, param)) return rc;
+    if (d_h && channel != BCHK_CHANNEL_RAYLEIGH)
+        return pfail(BCHK_EINVAL, "d_h must be NULL: channel %d has no fading factor", channel);
     if (!c || (B && !d_llr)) return pfail(BCHK_EINVAL, "NULL argument");
     if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
     if (B == 0) return 0;
@@ -1030,15 +1054,29 @@ int bchk_polar_generate_device(bchk_polar *c, double snr_db, size_t B, uint64_t 
     p.info = d_info;
     p.cw = d_cw;
     p.llr = d_llr;
+    p.fade = d_h;
+    p.y = d_y;
     p.word0 = word0;
     p.B = (uint32_t)B;
     p.seed_lo = (uint32_t)seed;
     p.seed_hi = (uint32_t)(seed >> 32);
     p.gen = 1;
-    p.sigma = sqrt(0.5 * pow(10, -snr_db / 10) * c->N / c->K);
-    p.var = p.sigma * p.sigma;  // CModem::SetNoiseVariance (Simulator.cpp:109)
+    p.channel = channel;
+    if (channel == BCHK_CHANNEL_BSC) {
+        p.cross = param;
+        p.sigma = p.var = 1.0;
+    } else {
+        p.sigma = sqrt(0.5 * pow(10, -param / 10) * c->N / c->K);
+        p.var = p.sigma * p.sigma;  // CModem::SetNoiseVariance (Simulator.cpp:109)
+    }
     PHIP_TRY(launch_polar_gen(p, stream ? (hipStream_t)stream : c->stream));
     return 0;
+}
+
+int bchk_polar_generate_device(bchk_polar *c, double snr_db, size_t B, uint64_t seed, uint64_t word0,
+                               uint8_t *d_info, uint8_t *d_cw, float *d_llr, void *stream) {
+    return bchk_polar_generate_channel_device(c, BCHK_CHANNEL_AWGN, snr_db, B, seed, word0, d_info, d_cw, d_llr,
+                                              nullptr, nullptr, stream);
 }
 
 int bchk_polar_count_device(bchk_polar *c, const uint8_t *d_info_tx, const uint8_t *d_cw_tx, const float *d_llr,
@@ -1065,18 +1103,22 @@ int bchk_polar_count_device(bchk_polar *c, const uint8_t *d_info_tx, const uint8
     return 0;
 }
 
-// The AWGN/BPSK simulation loop (CSimulator::Iterate over a range of Eb/N0) end to end on the
-// device: per point, batches are generated, decoded and counted until max_words words or
-// max_errors block errors. The batch that reaches max_errors is cut in word order from its
-// per-word flags and its prefix counted again (the decoded lists are still in the buffers),
-// and the next point starts at the word after the cut: the records depend on the arguments
-// only, not on `batch`.
-int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int points, uint64_t max_words,
-                            uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
-                            double *seconds, uint64_t *words_decoded) {
+// The BPSK simulation loop (CSimulator::Iterate over a range of Eb/N0 or, on the BSC, of
+// crossover probabilities) end to end on the device: per point, batches are generated, decoded
+// and counted until max_words words or max_errors block errors. The batch that reaches
+// max_errors is cut in word order from its per-word flags and its prefix counted again (the
+// decoded lists are still in the buffers), and the next point starts at the word after the cut:
+// the records depend on the arguments only, not on `batch`.
+int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from, double snr_step, int points,
+                                    uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                    bchk_polar_point *out, double *seconds, uint64_t *words_decoded) {
+    // every point's parameter, before any work (only the BSC's has a range)
+    for (int pt = 0; pt < (channel == BCHK_CHANNEL_BSC && points > 0 ? points : 1); ++pt)
+        if (int rc = polar_check_channel(channel, snr_from + pt * snr_step)) return rc;
     if (!c || !out) return pfail(BCHK_EINVAL, "NULL argument");
     if (points <= 0 || max_words == 0 || max_errors == 0)
         return pfail(BCHK_EINVAL, "points, max_words and max_errors must be positive");
+    if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
     const size_t N = (size_t)c->N, K = (size_t)std::max(c->K, 1), L = (size_t)c->L;
     const size_t per_word = 4 * N + L * (K + N) + 4 * L + 4 + K + N + 1;
     size_t Bm = batch;
@@ -1103,8 +1145,9 @@ int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int
         while (r.c[0] < max_words && r.c[1] < max_errors) {
             const size_t nb = (size_t)std::min<uint64_t>(Bm, max_words - r.c[0]);
             uint64_t h[8];
-            if ((rc = bchk_polar_generate_device(c, r.snr_db, nb, seed, word, (uint8_t *)c->txinfo.p,
-                                                 (uint8_t *)c->txcw.p, (float *)c->llr.p, s)) ||
+            if ((rc = bchk_polar_generate_channel_device(c, channel, r.snr_db, nb, seed, word, (uint8_t *)c->txinfo.p,
+                                                         (uint8_t *)c->txcw.p, (float *)c->llr.p, nullptr, nullptr,
+                                                         s)) ||
                 (rc = bchk_polar_decode_device(c, (const float *)c->llr.p, nb, (uint8_t *)c->info.p, (uint8_t *)c->cw.p,
                                                (float *)c->metric.p, (int32_t *)c->count.p, s)))
                 return rc;
@@ -1135,6 +1178,13 @@ int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (words_decoded) *words_decoded = decoded;
     return 0;
+}
+
+int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int points, uint64_t max_words,
+                            uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
+                            double *seconds, uint64_t *words_decoded) {
+    return bchk_polar_sweep_channel_device(c, BCHK_CHANNEL_AWGN, snr_from, snr_step, points, max_words, max_errors,
+                                           seed, batch, out, seconds, words_decoded);
 }
 
 // The genie kernel's layout, LDS size and persistent grid (once per context).
@@ -1219,10 +1269,11 @@ int bchk_polar_genie_device(bchk_polar *c, const uint8_t *d_info_tx, const float
     return 0;
 }
 
-// Words [word0, word0 + words) of the stream `seed` at snr_db through the genie kernel, in
-// batches; the sums are integers, so the result does not depend on `batch`.
-int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t seed, uint64_t word0, size_t batch,
-                         uint64_t *err, int64_t *soft, double *seconds) {
+// Words [word0, word0 + words) of the stream `seed` over `channel` at `param` through the genie
+// kernel, in batches; the sums are integers, so the result does not depend on `batch`.
+int bchk_polar_genie_run_channel(bchk_polar *c, int channel, double param, uint64_t words, uint64_t seed,
+                                 uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds) {
+    if (int rc = polar_check_channel(channel, param)) return rc;
     if (!c || !err || !soft) return pfail(BCHK_EINVAL, "NULL argument");
     if (words == 0 || words > (1ull << 31))
         return pfail(BCHK_EINVAL, "words must be 1..2^31 (the soft sums stay inside 64 bits)");
@@ -1249,8 +1300,8 @@ int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t 
     PHIP_TRY(hipMemsetAsync(c->gsum.p, 0, 16 * U, s));
     for (uint64_t done = 0; done < words;) {
         const size_t nb = (size_t)std::min<uint64_t>(Bm, words - done);
-        if ((rc = bchk_polar_generate_device(c, snr_db, nb, seed, word0 + done, (uint8_t *)c->txinfo.p, nullptr,
-                                             (float *)c->llr.p, s)) ||
+        if ((rc = bchk_polar_generate_channel_device(c, channel, param, nb, seed, word0 + done, (uint8_t *)c->txinfo.p,
+                                                     nullptr, (float *)c->llr.p, nullptr, nullptr, s)) ||
             (rc = bchk_polar_genie_device(c, (const uint8_t *)c->txinfo.p, (const float *)c->llr.p, nb, d_err, d_soft,
                                           nullptr, nullptr, s)))
             return rc;
@@ -1263,6 +1314,11 @@ int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t 
     memcpy(soft, h.data() + U, 8 * U);
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
+}
+
+int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t seed, uint64_t word0, size_t batch,
+                         uint64_t *err, int64_t *soft, double *seconds) {
+    return bchk_polar_genie_run_channel(c, BCHK_CHANNEL_AWGN, snr_db, words, seed, word0, batch, err, soft, seconds);
 }
 
 int bchk_polar_sync(bchk_polar *c) {
