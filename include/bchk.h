@@ -486,6 +486,49 @@ int bchk_polar_sweep_channel_device(bchk_polar *pc, int channel, double from, do
                                     uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
                                     bchk_polar_point *out, double *seconds, uint64_t *words_decoded);
 
+/* ---- Fixed-point SC-list decoding: int8 LLRs (csrc/polar_sclist_q8.hip). The
+ * vendored library's USE_INT8 configuration (SeqConfigOrig.h:186-194, SoftProcessing.cpp:643-1146)
+ * with symmetric saturation, for all-Arikan codes with every path's state in LDS. The contract:
+ *   sign       LLRs are int8_t, negative favours bit 1 (as everywhere at this boundary)
+ *   load       a value of -128 is read as -127; a punctured symbol loads 0, a shortened one +127
+ *   f step     f(a, b) = sgn(a) sgn(b) min(|a|, |b|), 0 if either operand is 0
+ *   g step     g(a, b, u) = clamp(u ? b - a : b + a, -127, +127)
+ *   decisions  the hard decision is v < 0; a decision against it costs |v|: R <- R - |v|
+ *   list       candidate order, kills, clones, free-index stack and final order are exactly those
+ *              of the f32 decoder (the same device routines)
+ *   metrics    written to the float metric buffer as exact integers (|R| <= 127 U < 2^24)
+ * So wherever no g step saturates, the lists are bit for bit those of bchk_polar_decode_* on the
+ * same values as floats. (The library's AVX path saturates at -128, where its abs wraps, and it
+ * loads 0x3F for a shortened symbol, MixedKernelEncoder.cpp:195; neither is followed.)
+ * Per path and symbol the state takes about 1.4 bytes instead of 4.4: (2048, 1024) at L = 32 and
+ * (4096, 2048) at L = 16 fit the 160 KiB. BCHK_EINVAL before any device call, with a message
+ * naming it, for a code with a matrix or named layer, and for a length whose int8 state exceeds
+ * 160 KiB. The context takes every other bchk_polar_* call (encode, generate, count, genie,
+ * state_info) but decodes only through the two calls below, which in turn refuse (BCHK_EINVAL)
+ * a context of any other bchk_polar_create*; bchk_polar_decode_* and bchk_polar_sweep_*device
+ * refuse this one. */
+int bchk_polar_create_q8(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out);
+/* llr [B][N] int8_t; info, cw, metric, count as bchk_polar_decode_host / _device. */
+int bchk_polar_decode_q8_host(bchk_polar *pc, const int8_t *llr, size_t B, uint8_t *info, uint8_t *cw,
+                              float *metric, int32_t *count);
+int bchk_polar_decode_q8_device(bchk_polar *pc, const int8_t *d_llr, size_t B, uint8_t *d_info, uint8_t *d_cw,
+                                float *d_metric, int32_t *d_count, void *stream);
+/* The demodulator's discretisation (NORMALIZE_MODEM, Modem.h:71-76) as one element-wise kernel on
+ * `stream` (NULL = the context's; any context): d_q[i] = clamp(rint(d_llr[i] * scale), -qmax,
+ * qmax) for i < count, the product formed in f32, ties to even, NaN -> 0, +-inf -> +-qmax.
+ * 1 <= qmax <= 127 (63 is the library's MTYPE_UPPER_BOUND for int8) and a positive finite scale,
+ * else BCHK_EINVAL; count = 0 is a no-op. */
+int bchk_polar_quantize_device(bchk_polar *pc, const float *d_llr, size_t count, float scale, int qmax, int8_t *d_q,
+                               void *stream);
+/* bchk_polar_sweep_channel_device on an int8 context: the same loop, stream, exact cut and
+ * channels, each batch going generate -> quantize (scale, qmax) -> int8 decode -> count (the
+ * counters read the channel's f32 LLRs). scale and qmax are checked as by
+ * bchk_polar_quantize_device before any work. */
+int bchk_polar_sweep_q8_device(bchk_polar *pc, int channel, double from, double step, int points,
+                               uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                               bchk_polar_point *out, double *seconds, uint64_t *words_decoded, float scale,
+                               int qmax);
+
 /* ---- BCH polar-kernel construction and the column-permutation search (root bchCoder.cpp;
  * csrc/kernel_search.hip). Kernels are row-major l x l bytes (0/1). */
 /* makeMatrix (root bchCoder.cpp:356-389): the nested extended-BCH kernel of size 2^power

@@ -47,7 +47,9 @@ EXPORTS = (
     "bchk_kernel_bec_masks", "bchk_kernel_bec_behaviour", "bchk_kernel_bec_sample", "bchk_kernel_bec_capacity",
     "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_polar_genie_device", "bchk_polar_genie_run",
     "bchk_polar_design_genie", "bchk_polar_generate_channel_device", "bchk_polar_sweep_channel_device",
-    "bchk_polar_genie_run_channel", "bchk_polar_design_genie_channel", "bchk_last_error", "bchk_version",
+    "bchk_polar_genie_run_channel", "bchk_polar_design_genie_channel",
+    "bchk_polar_create_q8", "bchk_polar_decode_q8_host", "bchk_polar_decode_q8_device",
+    "bchk_polar_quantize_device", "bchk_polar_sweep_q8_device", "bchk_last_error", "bchk_version",
 )
 
 # BCHK_CHANNEL_*: the channels of the polar simulation front-end
@@ -182,6 +184,12 @@ def lib():
     L.bchk_polar_genie_run_channel.argtypes = [vp, i32, dbl, u64, u64, u64, sz, vp, vp, C.POINTER(dbl)]
     L.bchk_polar_design_genie_channel.argtypes = [C.c_char_p, C.c_char_p, i32, i32, dbl, u64, u64, i32, vp, vp,
                                                   C.c_char_p, sz, C.POINTER(sz)]
+    L.bchk_polar_create_q8.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.bchk_polar_decode_q8_host.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.bchk_polar_decode_q8_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
+    L.bchk_polar_quantize_device.argtypes = [vp, vp, sz, C.c_float, i32, vp, vp]
+    L.bchk_polar_sweep_q8_device.argtypes = [vp, i32, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
+                                             C.POINTER(u64), C.c_float, i32]
     L.bchk_last_error.restype = C.c_char_p
     L.bchk_version.restype = C.c_char_p
     _lib = L
@@ -453,16 +461,29 @@ class PolarListDecoder:
     that state for codes with matrix or named layers (and all-Arikan ones, through the same
     kernel, csrc/polar_mixed_tiered.hip): the state of the layers before `split`, counted from the
     channel side, lives in the workspace; codes with an ordered-statistics layer
-    stay on state="lds"."""
+    stay on state="lds".
 
-    def __init__(self, spec, L, device=0, kernel_dir=None, state="lds", split=None):
+    llr="q8" (all-Arikan codes, state="lds" only) is the fixed-point decoder: decode
+    and decode_device take int8 LLRs (quantize / quantize_device make them), the path state is a
+    third of the f32 one's, and sweep_device needs a scale. llr="f32" is everything above."""
+
+    llr = "f32"  # the instance's number format ("q8": the fixed-point decoder)
+
+    def __init__(self, spec, L, device=0, kernel_dir=None, state="lds", split=None, llr="f32"):
         if state not in ("lds", "tiered", "tiered_mixed"):
             raise ValueError(f"state must be 'lds', 'tiered' or 'tiered_mixed', not {state!r}")
         if state == "lds" and split is not None:
             raise ValueError("split applies to the tiered states only")
+        if llr not in ("f32", "q8"):
+            raise ValueError(f"llr must be 'f32' or 'q8', not {llr!r}")
+        if llr == "q8" and state != "lds":
+            raise ValueError("llr='q8' keeps every path's state in LDS: state must be 'lds'")
+        self.llr = llr
         h = C.c_void_p()
         kdir = kernel_dir.encode() if kernel_dir else None
-        if state != "lds":
+        if llr == "q8":
+            _check(lib().bchk_polar_create_q8(spec.encode(), kdir, L, device, C.byref(h)))
+        elif state != "lds":
             create = lib().bchk_polar_create_tiered if state == "tiered" else lib().bchk_polar_create_tiered_mixed
             _check(create(spec.encode(), kdir, L, device, -1 if split is None else int(split), C.byref(h)))
         else:
@@ -510,19 +531,33 @@ class PolarListDecoder:
         return cw
 
     def decode(self, llr):
-        """llr [B][N] float32 -> (count [B], info [B][L][K], codewords [B][L][N], metrics [B][L])."""
-        llr = np.ascontiguousarray(llr, np.float32)
+        """llr [B][N] float32 -> (count [B], info [B][L][K], codewords [B][L][N], metrics [B][L]).
+        On a q8 decoder llr is int8 (an array of another type is refused, not converted)."""
+        if self.llr == "q8":
+            if np.asarray(llr).dtype != np.int8:
+                raise TypeError("a q8 decoder takes int8 LLRs (see quantize)")
+            llr = np.ascontiguousarray(llr, np.int8)
+            call = lib().bchk_polar_decode_q8_host
+        else:
+            llr = np.ascontiguousarray(llr, np.float32)
+            call = lib().bchk_polar_decode_host
         B = llr.shape[0]
         info = np.zeros((B, self.L, self.K), np.uint8)
         cw = np.zeros((B, self.L, self.N), np.uint8)
         met = np.zeros((B, self.L), np.float32)
         cnt = np.zeros(B, np.int32)
-        _check(lib().bchk_polar_decode_host(self._h, _p(llr), B, _p(info), _p(cw), _p(met), _p(cnt)))
+        _check(call(self._h, _p(llr), B, _p(info), _p(cw), _p(met), _p(cnt)))
         return cnt, info, cw, met
 
     def decode_device(self, d_llr, B, d_info, d_cw, d_metric, d_count, stream=None):
-        _check(lib().bchk_polar_decode_device(self._h, d_llr, B, d_info, d_cw, d_metric, d_count,
-                                              stream))
+        """Device pointers; d_llr [B][N] is f32, or int8 on a q8 decoder."""
+        call = lib().bchk_polar_decode_q8_device if self.llr == "q8" else lib().bchk_polar_decode_device
+        _check(call(self._h, d_llr, B, d_info, d_cw, d_metric, d_count, stream))
+
+    def quantize_device(self, d_llr, count, d_q, scale, qmax=63, stream=None):
+        """d_q[i] = clamp(rint(d_llr[i] * scale), -qmax, qmax), i < count (device pointers, f32 ->
+        int8): quantize() on the GPU, on any decoder."""
+        _check(lib().bchk_polar_quantize_device(self._h, d_llr or None, count, scale, qmax, d_q or None, stream))
 
     def encode_device(self, d_info, B, d_cw, stream=None):
         """The encoder on the GPU: d_info [B][K] u8 -> d_cw [B][N] u8 (device pointers)."""
@@ -548,17 +583,26 @@ class PolarListDecoder:
                                              d_info or None, d_cw or None, d_count or None, B, d_out8 or None,
                                              d_flags or None, stream))
 
-    def sweep_device(self, snr_from, snr_step, points, max_words, max_errors, seed=1, batch=0, channel="awgn"):
+    def sweep_device(self, snr_from, snr_step, points, max_words, max_errors, seed=1, batch=0, channel="awgn",
+                     scale=None, qmax=63):
         """The FER simulation end to end on the GPU: ([(snr_db, counters [8] ints)], seconds,
         words decoded). Each point runs until max_words words or max_errors block errors, cut
         exactly in word order; the word index runs on across points. channel as for
-        generate_device; on "bsc" the points are crossover probabilities."""
+        generate_device; on "bsc" the points are crossover probabilities. A q8 decoder needs
+        `scale` (each batch is quantised with (scale, qmax) as by quantize_device before it is
+        decoded); an f32 decoder refuses one."""
+        chan = _channel(channel)
+        if (scale is not None) != (self.llr == "q8"):
+            raise ValueError("scale is required on a q8 decoder" if self.llr == "q8"
+                             else "scale applies to a q8 decoder only")
         out = np.zeros(max(points, 0), POLAR_POINT_DTYPE)
         secs, words = C.c_double(0.0), C.c_uint64(0)
-        _check(lib().bchk_polar_sweep_channel_device(self._h, _channel(channel), snr_from, snr_step, points,
-                                                     max_words, max_errors, seed, batch,
-                                                     _p(out) if points > 0 else None, C.byref(secs),
-                                                     C.byref(words)))
+        args = (self._h, chan, snr_from, snr_step, points, max_words, max_errors, seed, batch,
+                _p(out) if points > 0 else None, C.byref(secs), C.byref(words))
+        if self.llr == "q8":
+            _check(lib().bchk_polar_sweep_q8_device(*args, scale, qmax))
+        else:
+            _check(lib().bchk_polar_sweep_channel_device(*args))
         return [(float(r["snr_db"]), [int(v) for v in r["c"]]) for r in out], secs.value, words.value
 
     def genie_device(self, d_info_tx, d_llr, B, d_err, d_soft, d_dec_llr=None, d_u=None, stream=None):
@@ -595,6 +639,18 @@ class PolarListDecoder:
         b, s = C.c_uint64(), C.c_uint64()
         _check(lib().bchk_polar_scratch_bytes(self._h, C.byref(b), C.byref(s)))
         return b.value, s.value
+
+
+def quantize(llr, scale, qmax=63):
+    """The rule of PolarListDecoder.quantize_device in numpy: int8 clamp(rint(llr * scale), -qmax,
+    qmax), the product formed in float32, ties to even, NaN -> 0, +-inf -> +-qmax."""
+    if not 1 <= int(qmax) <= 127:
+        raise ValueError(f"qmax = {qmax}: the int8 range is 1..127")
+    if not 0.0 < float(np.float32(scale)) < np.inf:
+        raise ValueError(f"scale = {scale} must be positive and finite")
+    with np.errstate(invalid="ignore", over="ignore"):
+        v = np.rint(np.asarray(llr, np.float32) * np.float32(scale))
+    return np.clip(np.where(np.isnan(v), np.float32(0), v), -qmax, qmax).astype(np.int8)
 
 
 def stream_skip(k, n, state, words):

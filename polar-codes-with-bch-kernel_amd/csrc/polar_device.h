@@ -1,6 +1,6 @@
 // polar_device.h -- what the host runtime (polar_host.cpp) shares with the gfx950 polar
 // kernels: the parameter blocks, LDS layouts and save-slot format of the SC-list decoders
-// (polar_sclist.hip, polar_mixed.hip), the simulation front-end (polar_channel.hip) and
+// (polar_sclist.hip, polar_sclist_q8.hip, polar_mixed.hip), the simulation front-end (polar_channel.hip) and
 // genie-aided SC (polar_genie.hip). PolarIo opens both decoder parameter blocks. The device
 // routines the kernels share are in polar_list_device.h (decisions, LoadLLRs),
 // polar_llr_device.h (SoftXOR, mixed-kernel LLRs and partial sums) and polar_tier_device.h (the
@@ -311,6 +311,29 @@ struct PolarListLayout {
 __host__ __device__ inline PolarListLayout polar_list_layout(int U, int L, int K, int pathCw) {
     PolarListLayout o;
     o.o_C = 4 * polar_path_s(U) * L;
+    o.o_act = (o.o_C + 4 * pathCw * L + 15) & ~15;
+    o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
+    return o;
+}
+
+// ---- the fixed-point all-Arikan kernel (polar_sclist_q8.hip): polar_sclist_kernel with int8
+// LLRs (the arithmetic contract: include/bchk.h). The block opens with PolarParams
+// and so with PolarIo: the map of LoadLLRs, the phase table and the output buffers are the f32
+// kernel's; io.llr is not read, the rows come from llr8.
+struct PolarQ8Params {
+    PolarParams p;
+    const int8_t *llr8;  // [B][N] channel LLRs, negative favours 1; -128 reads as -127
+};
+static_assert(offsetof(PolarQ8Params, llr8) == 160 && sizeof(PolarQ8Params) == 168, "PolarQ8Params layout");
+constexpr int kQ8Max = 127;  // the symmetric saturation bound; a shortened symbol's LLR
+
+// Per path S holds the U - 1 LLRs of the layers 1..n as bytes, layer λ at U - (U >> (λ-1)) as in
+// the f32 kernel: whole 16-byte pieces for the clone copy, and 16 bytes of padding, so that the
+// same word of consecutive paths falls in banks 4 apart. C, act and rec are polar_list_layout's.
+constexpr int polar_path_q8(int U) { return ((U + 15) & ~15) + 16; }
+__host__ __device__ inline PolarListLayout polar_q8_layout(int U, int L, int K, int pathCw) {
+    PolarListLayout o;
+    o.o_C = polar_path_q8(U) * L;
     o.o_act = (o.o_C + 4 * pathCw * L + 15) & ~15;
     o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
     return o;

@@ -40,6 +40,9 @@ hipError_t launch_polar_mixed(const PolarMixedParams &p, int grid, size_t lds, h
 const void *polar_mixed_kernel_ptr();
 hipError_t launch_polar_mixed_tiered(const PolarMixedTieredParams &p, int grid, size_t lds, hipStream_t s);  // polar_mixed_tiered.hip
 const void *polar_mixed_tiered_kernel_ptr();
+hipError_t launch_polar_q8(const PolarQ8Params &p, int grid, size_t lds, hipStream_t s);  // polar_sclist_q8.hip
+const void *polar_q8_kernel_ptr();
+hipError_t launch_polar_quantize(const float *llr, size_t count, float scale, int qmax, int8_t *q, hipStream_t s);
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
 hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s);
 hipError_t launch_polar_genie(const PolarGenieParams &p, int grid, size_t lds, hipStream_t s);  // polar_genie.hip
@@ -93,7 +96,7 @@ struct PBuf {
 }  // namespace
 
 struct bchk_polar {
-    enum class PolarState { List, Mixed, ListTiered, MixedTiered };
+    enum class PolarState { List, Mixed, ListTiered, MixedTiered, ListQ8 };
     int N = 0, K = 0, U = 0, n = 0, L = 0, device = 0;
     // layers: kernel size, Arikan flag, rows as bitmasks (bit c = K[r][c]); mixed = any
     // matrix or named (G / A5) layer (decoded by polar_mixed_kernel)
@@ -125,6 +128,7 @@ struct bchk_polar {
     int grid = 0;
     PBuf llr, info, cw, metric, count;
     PBuf txinfo, txcw, flags, cnt8;  // bchk_polar_sweep_device's sent words, error flags, counters
+    PBuf q8;                         // bchk_polar_sweep_q8_device's quantised LLRs
     // time-budgeted launches of codes with search layers (PolarMixedParams::budget)
     PBuf rstate, rsave, unfinished;
     uint64_t budget_ticks = 0;  // 100 MHz ticks per launch, 0 = one launch per call
@@ -137,7 +141,8 @@ struct bchk_polar {
     // Where the path state lives, and so which kernel decodes. ListTiered
     // (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`. MixedTiered
     // (polar_mixed_tiered.hip): the groups of the layers j < split in `ws`; tm.m holds the tiered
-    // layout, mp stays the LDS layout (the genie calls use it).
+    // layout, mp stays the LDS layout (the genie calls use it). ListQ8 (polar_sclist_q8.hip): List
+    // with int8 LLRs, decoded through bchk_polar_decode_q8_* only.
     PolarState state = PolarState::List;
     int split = 0, cwsplit = 0, cwall = 0;
     PBuf ws;  // [grid] workspaces of ws_bytes(c) each
@@ -582,6 +587,7 @@ const void *kernel_ptr(State st) {
     case State::Mixed: return polar_mixed_kernel_ptr();
     case State::ListTiered: return polar_tiered_kernel_ptr();
     case State::MixedTiered: return polar_mixed_tiered_kernel_ptr();
+    case State::ListQ8: return polar_q8_kernel_ptr();
     }
     return nullptr;
 }
@@ -633,6 +639,10 @@ int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, 
     return polar_create_tiered(spec, kdir, list_size, device, split, State::ListTiered, out);
 }
 
+int bchk_polar_create_q8(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out) {
+    return polar_create(spec, kdir, list_size, device, 0, State::ListQ8, out);
+}
+
 static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, State want,
                         bchk_polar **out) {
     if (!out || !spec) return pfail(BCHK_EINVAL, "NULL argument");
@@ -667,6 +677,17 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         c->cwall = off[c->n] + 1;
         c->cwsplit = split < c->n ? off[split + 1] : c->cwall;
         c->lds = tiered_layout(c, split).bytes;
+    } else if (want == State::ListQ8) {
+        for (int j = 0; j < c->n; ++j)
+            if (!c->arikan[j]) {
+                std::istringstream in(spec);
+                std::string name;
+                for (int t = 0; t < 6 + j + 1; ++t) in >> name;  // the header's six numbers, then the layers
+                return pfail(BCHK_EINVAL, "the int8 decoder is built for all-Arikan codes: layer %d is \"%s\"", j,
+                             name.c_str());
+            }
+        c->state = State::ListQ8;
+        c->lds = polar_q8_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     } else if (c->mixed) {
         if (int rc = mixed_tables(c)) return rc;
         c->state = State::Mixed;
@@ -785,11 +806,9 @@ int bchk_polar_params(const bchk_polar *c, int *n, int *k, int *unshortened, int
     return 0;
 }
 
-int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_t *d_info,
-                             uint8_t *d_cw, float *d_metric, int32_t *d_count, void *stream) {
-    if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
-    if (B == 0) return 0;
-    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+// the caller's buffers and the context's tables, as every decode launch takes them
+static PolarIo polar_io(const bchk_polar *c, const float *d_llr, uint8_t *d_info, uint8_t *d_cw, float *d_metric,
+                        int32_t *d_count) {
     PolarIo io{};
     io.llr = d_llr;
     io.info = d_info;
@@ -800,20 +819,33 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
     io.phase = reinterpret_cast<const uint16_t *>(c->d_tab + c->off_phase);
     io.cwpos = reinterpret_cast<const int16_t *>(c->d_tab + c->off_cwpos);
     io.dfcorr = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_dfcorr);
+    return io;
+}
+// the parameter block of the all-Arikan kernels (f32, tiered, int8)
+static PolarParams polar_list_params(const bchk_polar *c, const PolarIo &io, size_t B) {
+    PolarParams p{};
+    p.io = io;
+    p.B = (uint32_t)B;
+    p.pathCw = polar_cw_layout(c->U, p.cwoff);
+    p.n = c->n;
+    p.U = c->U;
+    p.N = c->N;
+    p.K = c->K;
+    p.L = c->L;
+    return p;
+}
+
+int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_t *d_info,
+                             uint8_t *d_cw, float *d_metric, int32_t *d_count, void *stream) {
+    if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
+    if (c->state == State::ListQ8)
+        return pfail(BCHK_EINVAL, "an int8 context (bchk_polar_create_q8) decodes through bchk_polar_decode_q8_* only");
+    if (B == 0) return 0;
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    const PolarIo io = polar_io(c, d_llr, d_info, d_cw, d_metric, d_count);
     const int grid = (int)std::min<size_t>((size_t)c->grid, B);  // tiered: <= the workspaces allocated at create
     const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    auto list_params = [&]() {
-        PolarParams p{};
-        p.io = io;
-        p.B = (uint32_t)B;
-        p.pathCw = polar_cw_layout(c->U, p.cwoff);
-        p.n = c->n;
-        p.U = c->U;
-        p.N = c->N;
-        p.K = c->K;
-        p.L = c->L;
-        return p;
-    };
+    auto list_params = [&]() { return polar_list_params(c, io, B); };
     auto mixed_params = [&](PolarMixedParams m) {  // m: the state's layout
         m.io = io;
         m.krows = reinterpret_cast<const uint64_t *>(c->d_tab + c->off_krows);
@@ -849,6 +881,7 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
         return 0;
     }
     case State::Mixed:
+    case State::ListQ8:  // (refused above)
         break;
     }
     PolarMixedParams m = mixed_params(c->mp);
@@ -903,30 +936,72 @@ int bchk_polar_state_info(const bchk_polar *c, int *split, uint64_t *lds_bytes, 
     return 0;
 }
 
-int bchk_polar_decode_host(bchk_polar *c, const float *llr, size_t B, uint8_t *info, uint8_t *cw,
-                           float *metric, int32_t *count) {
+// The int8 decoder (polar_sclist_q8.hip): d_llr [B][N] int8, the outputs as bchk_polar_decode_device.
+int bchk_polar_decode_q8_device(bchk_polar *c, const int8_t *d_llr, size_t B, uint8_t *d_info, uint8_t *d_cw,
+                                float *d_metric, int32_t *d_count, void *stream) {
+    if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
+    if (c->state != State::ListQ8)
+        return pfail(BCHK_EINVAL, "bchk_polar_decode_q8_* take a context of bchk_polar_create_q8 (this one decodes f32 LLRs)");
+    if (B == 0) return 0;
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    PolarQ8Params q{};
+    q.p = polar_list_params(c, polar_io(c, nullptr, d_info, d_cw, d_metric, d_count), B);
+    q.llr8 = d_llr;
+    PHIP_TRY(launch_polar_q8(q, (int)std::min<size_t>((size_t)c->grid, B), c->lds, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
+
+// both host decodes: rows of `elem` bytes per LLR (4: f32, 1: int8) through the context's buffers
+static int polar_decode_host(bchk_polar *c, const void *llr, size_t elem, size_t B, uint8_t *info, uint8_t *cw,
+                             float *metric, int32_t *count) {
     if (!c || (B && (!llr || !info || !metric || !count))) return pfail(BCHK_EINVAL, "NULL argument");
+    if ((elem == 1) != (c->state == State::ListQ8))  // before any copy; the device entries name the reason
+        return elem == 1 ? bchk_polar_decode_q8_device(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr)
+                         : bchk_polar_decode_device(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (B == 0) return 0;
     const size_t L = (size_t)c->L;
     int rc;
-    if ((rc = c->llr.ensure(B * c->N * sizeof(float))) || (rc = c->info.ensure(B * L * std::max(c->K, 1))) ||
+    if ((rc = c->llr.ensure(B * c->N * elem)) || (rc = c->info.ensure(B * L * std::max(c->K, 1))) ||
         (rc = c->metric.ensure(B * L * sizeof(float))) || (rc = c->count.ensure(B * sizeof(int32_t))) ||
         (cw && (rc = c->cw.ensure(B * L * c->N))))
         return rc;
-    PHIP_TRY(hipMemcpyAsync(c->llr.p, llr, B * c->N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    PHIP_TRY(hipMemcpyAsync(c->llr.p, llr, B * c->N * elem, hipMemcpyHostToDevice, c->stream));
     // list rows past each count keep the caller's contents, as the reference leaves them
     PHIP_TRY(hipMemcpyAsync(c->info.p, info, B * L * c->K, hipMemcpyHostToDevice, c->stream));
     PHIP_TRY(hipMemcpyAsync(c->metric.p, metric, B * L * sizeof(float), hipMemcpyHostToDevice, c->stream));
     if (cw) PHIP_TRY(hipMemcpyAsync(c->cw.p, cw, B * L * c->N, hipMemcpyHostToDevice, c->stream));
-    if ((rc = bchk_polar_decode_device(c, (const float *)c->llr.p, B, (uint8_t *)c->info.p,
-                                       cw ? (uint8_t *)c->cw.p : nullptr, (float *)c->metric.p,
-                                       (int32_t *)c->count.p, c->stream)))
+    uint8_t *const d_cw = cw ? (uint8_t *)c->cw.p : nullptr;
+    if ((rc = elem == 1 ? bchk_polar_decode_q8_device(c, (const int8_t *)c->llr.p, B, (uint8_t *)c->info.p, d_cw,
+                                                      (float *)c->metric.p, (int32_t *)c->count.p, c->stream)
+                        : bchk_polar_decode_device(c, (const float *)c->llr.p, B, (uint8_t *)c->info.p, d_cw,
+                                                   (float *)c->metric.p, (int32_t *)c->count.p, c->stream)))
         return rc;
     PHIP_TRY(hipMemcpyAsync(info, c->info.p, B * L * c->K, hipMemcpyDeviceToHost, c->stream));
     PHIP_TRY(hipMemcpyAsync(metric, c->metric.p, B * L * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     PHIP_TRY(hipMemcpyAsync(count, c->count.p, B * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     if (cw) PHIP_TRY(hipMemcpyAsync(cw, c->cw.p, B * L * c->N, hipMemcpyDeviceToHost, c->stream));
     PHIP_TRY(hipStreamSynchronize(c->stream));
+    return 0;
+}
+
+int bchk_polar_decode_host(bchk_polar *c, const float *llr, size_t B, uint8_t *info, uint8_t *cw,
+                           float *metric, int32_t *count) {
+    return polar_decode_host(c, llr, sizeof(float), B, info, cw, metric, count);
+}
+
+int bchk_polar_decode_q8_host(bchk_polar *c, const int8_t *llr, size_t B, uint8_t *info, uint8_t *cw,
+                              float *metric, int32_t *count) {
+    return polar_decode_host(c, llr, 1, B, info, cw, metric, count);
+}
+
+// q = clamp(rint(llr scale), -qmax, qmax), ties to even, NaN -> 0 (polar_sclist_q8.hip)
+int bchk_polar_quantize_device(bchk_polar *c, const float *d_llr, size_t count, float scale, int qmax, int8_t *d_q,
+                               void *stream) {
+    if (qmax < 1 || qmax > kQ8Max) return pfail(BCHK_EINVAL, "qmax = %d: the int8 range is 1..%d", qmax, kQ8Max);
+    if (!(scale > 0.0f) || std::isinf(scale)) return pfail(BCHK_EINVAL, "scale = %g must be positive and finite", scale);
+    if (!c || (count && (!d_llr || !d_q))) return pfail(BCHK_EINVAL, "NULL argument");
+    if (count == 0) return 0;
+    PHIP_TRY(launch_polar_quantize(d_llr, count, scale, qmax, d_q, stream ? (hipStream_t)stream : c->stream));
     return 0;
 }
 
@@ -1109,13 +1184,20 @@ int bchk_polar_count_device(bchk_polar *c, const uint8_t *d_info_tx, const uint8
 // max_errors is cut in word order from its per-word flags and its prefix counted again (the
 // decoded lists are still in the buffers), and the next point starts at the word after the cut:
 // the records depend on the arguments only, not on `batch`.
-int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from, double snr_step, int points,
-                                    uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
-                                    bchk_polar_point *out, double *seconds, uint64_t *words_decoded) {
+// q8: each batch's LLRs are quantised (scale, qmax) and decoded by the int8 kernel; the counters
+// still read the channel's f32 LLRs.
+static int polar_sweep(bchk_polar *c, int channel, double snr_from, double snr_step, int points, uint64_t max_words,
+                       uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out, double *seconds,
+                       uint64_t *words_decoded, bool q8, float scale, int qmax) {
     // every point's parameter, before any work (only the BSC's has a range)
     for (int pt = 0; pt < (channel == BCHK_CHANNEL_BSC && points > 0 ? points : 1); ++pt)
         if (int rc = polar_check_channel(channel, snr_from + pt * snr_step)) return rc;
     if (!c || !out) return pfail(BCHK_EINVAL, "NULL argument");
+    if (q8 != (c->state == State::ListQ8))
+        return pfail(BCHK_EINVAL, q8 ? "bchk_polar_sweep_q8_device takes a context of bchk_polar_create_q8"
+                                     : "an int8 context (bchk_polar_create_q8) sweeps through bchk_polar_sweep_q8_device");
+    if (q8)  // scale and qmax, checked as every batch would
+        if (int rc = bchk_polar_quantize_device(c, nullptr, 0, scale, qmax, nullptr, nullptr)) return rc;
     if (points <= 0 || max_words == 0 || max_errors == 0)
         return pfail(BCHK_EINVAL, "points, max_words and max_errors must be positive");
     if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
@@ -1131,7 +1213,8 @@ int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from,
     if ((rc = c->llr.ensure(Bm * N * sizeof(float))) || (rc = c->info.ensure(Bm * L * K)) ||
         (rc = c->cw.ensure(Bm * L * N)) || (rc = c->metric.ensure(Bm * L * sizeof(float))) ||
         (rc = c->count.ensure(Bm * sizeof(int32_t))) || (rc = c->txinfo.ensure(Bm * K)) ||
-        (rc = c->txcw.ensure(Bm * N)) || (rc = c->flags.ensure(Bm)) || (rc = c->cnt8.ensure(8 * sizeof(uint64_t))))
+        (rc = c->txcw.ensure(Bm * N)) || (rc = c->flags.ensure(Bm)) || (rc = c->cnt8.ensure(8 * sizeof(uint64_t))) ||
+        (q8 && (rc = c->q8.ensure(Bm * N))))
         return rc;
     const hipStream_t s = c->stream;
     uint64_t *d8 = (uint64_t *)c->cnt8.p;
@@ -1147,10 +1230,20 @@ int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from,
             uint64_t h[8];
             if ((rc = bchk_polar_generate_channel_device(c, channel, r.snr_db, nb, seed, word, (uint8_t *)c->txinfo.p,
                                                          (uint8_t *)c->txcw.p, (float *)c->llr.p, nullptr, nullptr,
-                                                         s)) ||
-                (rc = bchk_polar_decode_device(c, (const float *)c->llr.p, nb, (uint8_t *)c->info.p, (uint8_t *)c->cw.p,
-                                               (float *)c->metric.p, (int32_t *)c->count.p, s)))
+                                                         s)))
                 return rc;
+            if (q8) {
+                if ((rc = bchk_polar_quantize_device(c, (const float *)c->llr.p, nb * N, scale, qmax, (int8_t *)c->q8.p,
+                                                     s)) ||
+                    (rc = bchk_polar_decode_q8_device(c, (const int8_t *)c->q8.p, nb, (uint8_t *)c->info.p,
+                                                      (uint8_t *)c->cw.p, (float *)c->metric.p, (int32_t *)c->count.p,
+                                                      s)))
+                    return rc;
+            } else if ((rc = bchk_polar_decode_device(c, (const float *)c->llr.p, nb, (uint8_t *)c->info.p,
+                                                      (uint8_t *)c->cw.p, (float *)c->metric.p, (int32_t *)c->count.p,
+                                                      s))) {
+                return rc;
+            }
             decoded += nb;
             size_t used = nb;
             for (int pass = 0; pass < 2; ++pass) {  // the whole batch, then its prefix up to the cut
@@ -1178,6 +1271,22 @@ int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from,
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     if (words_decoded) *words_decoded = decoded;
     return 0;
+}
+
+int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from, double snr_step, int points,
+                                    uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                    bchk_polar_point *out, double *seconds, uint64_t *words_decoded) {
+    return polar_sweep(c, channel, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
+                       words_decoded, false, 0.0f, 0);
+}
+
+// The same loop through the int8 decoder: generate -> quantize (scale, qmax) -> q8 decode -> count.
+int bchk_polar_sweep_q8_device(bchk_polar *c, int channel, double snr_from, double snr_step, int points,
+                               uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                               bchk_polar_point *out, double *seconds, uint64_t *words_decoded, float scale,
+                               int qmax) {
+    return polar_sweep(c, channel, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
+                       words_decoded, true, scale, qmax);
 }
 
 int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int points, uint64_t max_words,

@@ -1,5 +1,6 @@
 // polar_list_device.h -- the list bookkeeping of SC-list decoding, shared by the all-Arikan
-// kernels (polar_sclist.hip, polar_sclist_tiered.hip) and the mixed-kernel ones (polar_mixed.hip, polar_mixed_tiered.hip): one copy of the
+// kernels (polar_sclist.hip, polar_sclist_tiered.hip, and polar_sclist_q8.hip, whose int8 leaf LLRs
+// and integer metrics are exact as floats) and the mixed-kernel ones (polar_mixed.hip, polar_mixed_tiered.hip): one copy of the
 // reference's CMixedKernelListDecoder (out/external/MixedKernelListDecoder.cpp:61-268) over the
 // path-index stack of out/external/TVMemoryEngine.cpp:85-142, so both kernels take the same
 // decisions with the same tie-breaks and path indices. Also LoadLLRs (chan_llr, every polar
