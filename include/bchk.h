@@ -508,6 +508,20 @@ int bchk_polar_sweep_channel_device(bchk_polar *pc, int channel, double from, do
  * a context of any other bchk_polar_create*; bchk_polar_decode_* and bchk_polar_sweep_*device
  * refuse this one. */
 int bchk_polar_create_q8(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out);
+/* The int8 decoder past the LDS budget (csrc/polar_sclist_q8_tiered.hip): the
+ * contract above in the tiered state of bchk_polar_create_tiered. The layers 1..split of every
+ * path lie in a per-workgroup device-memory workspace, the LLRs as bytes (about 1.4 U L bytes per
+ * workgroup where the f32 tiered state takes 4.4 U L), so every all-Arikan code up to U = 16384
+ * decodes at every list size up to 32, and where bchk_polar_create_q8 also takes the code the
+ * lists are its lists bit for bit. split = -1: the rule of bchk_polar_create_tiered applied to
+ * this state's LDS bytes; 1..layers is taken as given. BCHK_EINVAL before any device call, with a
+ * message, for a matrix or named layer (named as above), a split outside -1 and 1..layers,
+ * U > 16384, a list size outside 1..32, and an LDS part above 160 KiB at the split asked for.
+ * Workspace, its bound (BCHK_POLAR_WORKSPACE_MB), bchk_polar_state_info and
+ * bchk_polar_scratch_bytes as for bchk_polar_create_tiered; the context is an int8 context in
+ * every call: it decodes and sweeps through the bchk_polar_*_q8_* calls below only. */
+int bchk_polar_create_q8_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
+                                bchk_polar **out);
 /* llr [B][N] int8_t; info, cw, metric, count as bchk_polar_decode_host / _device. */
 int bchk_polar_decode_q8_host(bchk_polar *pc, const int8_t *llr, size_t B, uint8_t *info, uint8_t *cw,
                               float *metric, int32_t *count);

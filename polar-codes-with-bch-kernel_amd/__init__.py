@@ -48,7 +48,7 @@ EXPORTS = (
     "bchk_kernel_write_file", "bchk_polar_design_bec", "bchk_polar_genie_device", "bchk_polar_genie_run",
     "bchk_polar_design_genie", "bchk_polar_generate_channel_device", "bchk_polar_sweep_channel_device",
     "bchk_polar_genie_run_channel", "bchk_polar_design_genie_channel",
-    "bchk_polar_create_q8", "bchk_polar_decode_q8_host", "bchk_polar_decode_q8_device",
+    "bchk_polar_create_q8", "bchk_polar_create_q8_tiered", "bchk_polar_decode_q8_host", "bchk_polar_decode_q8_device",
     "bchk_polar_quantize_device", "bchk_polar_sweep_q8_device", "bchk_last_error", "bchk_version",
 )
 
@@ -185,6 +185,7 @@ def lib():
     L.bchk_polar_design_genie_channel.argtypes = [C.c_char_p, C.c_char_p, i32, i32, dbl, u64, u64, i32, vp, vp,
                                                   C.c_char_p, sz, C.POINTER(sz)]
     L.bchk_polar_create_q8.argtypes = [C.c_char_p, C.c_char_p, i32, i32, C.POINTER(vp)]
+    L.bchk_polar_create_q8_tiered.argtypes = [C.c_char_p, C.c_char_p, i32, i32, i32, C.POINTER(vp)]
     L.bchk_polar_decode_q8_host.argtypes = [vp, vp, sz, vp, vp, vp, vp]
     L.bchk_polar_decode_q8_device.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp]
     L.bchk_polar_quantize_device.argtypes = [vp, vp, sz, C.c_float, i32, vp, vp]
@@ -463,25 +464,34 @@ class PolarListDecoder:
     channel side, lives in the workspace; codes with an ordered-statistics layer
     stay on state="lds".
 
-    llr="q8" (all-Arikan codes, state="lds" only) is the fixed-point decoder: decode
-    and decode_device take int8 LLRs (quantize / quantize_device make them), the path state is a
-    third of the f32 one's, and sweep_device needs a scale. llr="f32" is everything above."""
+    llr="q8" (all-Arikan codes) is the fixed-point decoder: decode and decode_device
+    take int8 LLRs (quantize / quantize_device make them), the path state is a third of the f32
+    one's, and sweep_device needs a scale. With state="lds" every path's state is in LDS (about
+    U L <= 65536); state="tiered_q8" (U <= 16384, any L <= 32; llr="q8" only) is that decoder in
+    the tiered state (csrc/polar_sclist_q8_tiered.hip): the layers 1..split in the
+    workspace with the LLRs as bytes, the same lists bit for bit, split=None as for "tiered".
+    llr="f32" is everything above."""
 
     llr = "f32"  # the instance's number format ("q8": the fixed-point decoder)
 
     def __init__(self, spec, L, device=0, kernel_dir=None, state="lds", split=None, llr="f32"):
-        if state not in ("lds", "tiered", "tiered_mixed"):
-            raise ValueError(f"state must be 'lds', 'tiered' or 'tiered_mixed', not {state!r}")
+        if state not in ("lds", "tiered", "tiered_mixed", "tiered_q8"):
+            raise ValueError(f"state must be 'lds', 'tiered', 'tiered_mixed' or 'tiered_q8', not {state!r}")
         if state == "lds" and split is not None:
             raise ValueError("split applies to the tiered states only")
         if llr not in ("f32", "q8"):
             raise ValueError(f"llr must be 'f32' or 'q8', not {llr!r}")
-        if llr == "q8" and state != "lds":
-            raise ValueError("llr='q8' keeps every path's state in LDS: state must be 'lds'")
+        if llr == "q8" and state not in ("lds", "tiered_q8"):
+            raise ValueError("llr='q8' takes state='lds' or, for the tiered state, state='tiered_q8'")
+        if state == "tiered_q8" and llr != "q8":
+            raise ValueError("state='tiered_q8' is the fixed-point decoder: llr must be 'q8'")
         self.llr = llr
         h = C.c_void_p()
         kdir = kernel_dir.encode() if kernel_dir else None
-        if llr == "q8":
+        if state == "tiered_q8":
+            _check(lib().bchk_polar_create_q8_tiered(spec.encode(), kdir, L, device, -1 if split is None else int(split),
+                                                     C.byref(h)))
+        elif llr == "q8":
             _check(lib().bchk_polar_create_q8(spec.encode(), kdir, L, device, C.byref(h)))
         elif state != "lds":
             create = lib().bchk_polar_create_tiered if state == "tiered" else lib().bchk_polar_create_tiered_mixed

@@ -361,7 +361,7 @@ constexpr int polar_cw_words(int U, int lam) {
 // float L (U - (U >> (λ-1))); at w_C, L arrays per packed layer, layer λ at word L cwoff[λ]
 // (C_0's arrays belong to the paths, the others are shared through idx).
 struct PolarTieredLayout {
-    int pathS, pathC, n_C;  // LDS strides per path (floats, words) and the C words in use
+    int pathS, pathC, n_C;  // LDS strides per path (floats -- bytes in the q8 layout --, words) and the C words in use
     int o_C, o_idx, o_own, o_act;
     uint32_t bytes;
     uint64_t w_C, ws_bytes;
@@ -379,6 +379,39 @@ __host__ __device__ inline PolarTieredLayout polar_tiered_layout(int U, int L, i
     o.o_act = (o.o_own + L + 15) & ~15;
     o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
     o.w_C = (4ull * (uint64_t)L * (uint64_t)(U - Us) + 15ull) & ~15ull;
+    o.ws_bytes = (o.w_C + 4ull * (uint64_t)L * (uint64_t)cwsplit + 255ull) & ~255ull;
+    return o;
+}
+
+// ---- the tiered fixed-point all-Arikan kernel (polar_sclist_q8_tiered.hip): the tiered kernel
+// with the int8 LLRs of polar_sclist_q8.hip. The block opens with
+// PolarTieredParams; io.llr is not read, the rows come from llr8.
+struct PolarQ8TieredParams {
+    PolarTieredParams t;
+    const int8_t *llr8;  // [B][N] channel LLRs, as PolarQ8Params::llr8
+};
+static_assert(offsetof(PolarTieredParams, ws) == 160 && offsetof(PolarTieredParams, split) == 168 &&
+                  offsetof(PolarQ8TieredParams, llr8) == 184 && sizeof(PolarQ8TieredParams) == 192,
+              "PolarQ8TieredParams layout");
+// polar_tiered_layout with byte LLRs (pathS counts bytes here). LDS: per path the S layers
+// split+1 .. n in polar_path_q8's form for the sub-code, layer λ at byte (U >> split) - (U >> (λ-1));
+// C, idx, own, act and rec as in the f32 tiered layout.
+// Workspace of one workgroup: per global layer λ = 1..split L arrays of U >> λ bytes, layer λ at
+// byte L (U - (U >> (λ-1))) -- so an array of at least 4 bytes starts on a dword and one of at
+// least 16 on 16 -- and at w_C the packed C arrays exactly as the f32 tiered kernel has them.
+__host__ __device__ inline PolarTieredLayout polar_q8_tiered_layout(int U, int L, int K, int split, int cwsplit,
+                                                                    int cwall) {
+    PolarTieredLayout o;
+    const int Us = U >> split;
+    o.pathS = Us > 1 ? polar_path_q8(Us) : 0;
+    o.n_C = cwall - cwsplit;
+    o.pathC = o.n_C ? (o.n_C | 1) : 0;
+    o.o_C = o.pathS * L;
+    o.o_idx = o.o_C + 4 * o.pathC * L;
+    o.o_own = o.o_idx + split * L;
+    o.o_act = (o.o_own + L + 15) & ~15;
+    o.bytes = (uint32_t)((o.o_act + 4 * L + 4 * L * polar_rec_words(K) + 15) & ~15);
+    o.w_C = ((uint64_t)L * (uint64_t)(U - Us) + 15ull) & ~15ull;
     o.ws_bytes = (o.w_C + 4ull * (uint64_t)L * (uint64_t)cwsplit + 255ull) & ~255ull;
     return o;
 }

@@ -42,6 +42,8 @@ hipError_t launch_polar_mixed_tiered(const PolarMixedTieredParams &p, int grid, 
 const void *polar_mixed_tiered_kernel_ptr();
 hipError_t launch_polar_q8(const PolarQ8Params &p, int grid, size_t lds, hipStream_t s);  // polar_sclist_q8.hip
 const void *polar_q8_kernel_ptr();
+hipError_t launch_polar_q8_tiered(const PolarQ8TieredParams &p, int grid, size_t lds, hipStream_t s);  // polar_sclist_q8_tiered.hip
+const void *polar_q8_tiered_kernel_ptr();
 hipError_t launch_polar_quantize(const float *llr, size_t count, float scale, int qmax, int8_t *q, hipStream_t s);
 hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s);      // polar_channel.hip
 hipError_t launch_polar_count(const PolarCountParams &p, hipStream_t s);
@@ -96,7 +98,7 @@ struct PBuf {
 }  // namespace
 
 struct bchk_polar {
-    enum class PolarState { List, Mixed, ListTiered, MixedTiered, ListQ8 };
+    enum class PolarState { List, Mixed, ListTiered, MixedTiered, ListQ8, ListQ8Tiered };
     int N = 0, K = 0, U = 0, n = 0, L = 0, device = 0;
     // layers: kernel size, Arikan flag, rows as bitmasks (bit c = K[r][c]); mixed = any
     // matrix or named (G / A5) layer (decoded by polar_mixed_kernel)
@@ -142,12 +144,16 @@ struct bchk_polar {
     // (polar_sclist_tiered.hip): layers 1..split and C_0 of every path in `ws`. MixedTiered
     // (polar_mixed_tiered.hip): the groups of the layers j < split in `ws`; tm.m holds the tiered
     // layout, mp stays the LDS layout (the genie calls use it). ListQ8 (polar_sclist_q8.hip): List
-    // with int8 LLRs, decoded through bchk_polar_decode_q8_* only.
+    // with int8 LLRs, decoded through bchk_polar_decode_q8_* only. ListQ8Tiered
+    // (polar_sclist_q8_tiered.hip): ListTiered with int8 LLRs, through the same calls.
     PolarState state = PolarState::List;
     int split = 0, cwsplit = 0, cwall = 0;
     PBuf ws;  // [grid] workspaces of ws_bytes(c) each
     PolarMixedTieredParams tm{};
-    bool is_tiered() const { return state == PolarState::ListTiered || state == PolarState::MixedTiered; }
+    bool is_tiered() const {
+        return state == PolarState::ListTiered || state == PolarState::MixedTiered || state == PolarState::ListQ8Tiered;
+    }
+    bool is_q8() const { return state == PolarState::ListQ8 || state == PolarState::ListQ8Tiered; }  // an int8 context
 };
 using State = bchk_polar::PolarState;
 
@@ -155,12 +161,14 @@ namespace {
 
 constexpr size_t kPolarLdsMax = 160 * 1024;
 
-// the tiered kernel's LDS and workspace layout at `split` (polar_device.h)
-PolarTieredLayout tiered_layout(const bchk_polar *c, int split) {
+// the tiered kernels' LDS and workspace layout at `split` (polar_device.h), f32 or int8 LLRs
+PolarTieredLayout tiered_layout(const bchk_polar *c, int split, bool q8 = false) {
     int32_t off[kPolarMaxLayers + 1];
     (void)polar_cw_layout(c->U, off);
     const int words = off[c->n] + 1;  // C_n is one word
-    return polar_tiered_layout(c->U, c->L, c->K, split, split < c->n ? off[split + 1] : words, words);
+    const int cwsplit = split < c->n ? off[split + 1] : words;
+    return q8 ? polar_q8_tiered_layout(c->U, c->L, c->K, split, cwsplit, words)
+              : polar_tiered_layout(c->U, c->L, c->K, split, cwsplit, words);
 }
 // Waves per CU that LDS allows, up to kTieredWaves: past that the decoder is bound by the
 // latency of its global layers, not by the waves in flight.
@@ -566,6 +574,7 @@ size_t mixed_tiered_lds_at(const bchk_polar *c, int split) {
 uint64_t ws_bytes(const bchk_polar *c) {
     switch (c->state) {
     case State::ListTiered: return tiered_layout(c, c->split).ws_bytes;
+    case State::ListQ8Tiered: return tiered_layout(c, c->split, true).ws_bytes;
     case State::MixedTiered: return mixed_tiered_lds(c, c->tm).ws_bytes;
     default: return 0;
     }
@@ -588,6 +597,7 @@ const void *kernel_ptr(State st) {
     case State::ListTiered: return polar_tiered_kernel_ptr();
     case State::MixedTiered: return polar_mixed_tiered_kernel_ptr();
     case State::ListQ8: return polar_q8_kernel_ptr();
+    case State::ListQ8Tiered: return polar_q8_tiered_kernel_ptr();
     }
     return nullptr;
 }
@@ -619,7 +629,7 @@ int bchk_polar_create_kdir(const char *spec, const char *kdir, int list_size, in
     return polar_create(spec, kdir, list_size, device, 0, State::List, out);
 }
 
-// the checked entry of both tiered states
+// the checked entry of the tiered states
 static int polar_create_tiered(const char *spec, const char *kdir, int list_size, int device, int split, State want,
                                bchk_polar **out) {
     if (split == 0 || split < -1) {
@@ -641,6 +651,24 @@ int bchk_polar_create_tiered(const char *spec, const char *kdir, int list_size, 
 
 int bchk_polar_create_q8(const char *spec, const char *kdir, int list_size, int device, bchk_polar **out) {
     return polar_create(spec, kdir, list_size, device, 0, State::ListQ8, out);
+}
+
+int bchk_polar_create_q8_tiered(const char *spec, const char *kdir, int list_size, int device, int split,
+                                bchk_polar **out) {
+    return polar_create_tiered(spec, kdir, list_size, device, split, State::ListQ8Tiered, out);
+}
+
+// both int8 states: the first layer that is not Arikan is refused by name
+static int q8_all_arikan(const bchk_polar *c, const char *spec) {
+    for (int j = 0; j < c->n; ++j)
+        if (!c->arikan[j]) {
+            std::istringstream in(spec);
+            std::string name;
+            for (int t = 0; t < 6 + j + 1; ++t) in >> name;  // the header's six numbers, then the layers
+            return pfail(BCHK_EINVAL, "the int8 decoder is built for all-Arikan codes: layer %d is \"%s\"", j,
+                         name.c_str());
+        }
+    return 0;
 }
 
 static int polar_create(const char *spec, const char *kdir, int list_size, int device, int split, State want,
@@ -666,26 +694,24 @@ static int polar_create(const char *spec, const char *kdir, int list_size, int d
         c->split = split;
         mixed_tiered_layout(c, split, c->tm);
         c->lds = mixed_tiered_lds(c, c->tm).bytes;
-    } else if (want == State::ListTiered) {
-        if (c->mixed) return pfail(BCHK_EINVAL, "tiered state is built for all-Arikan codes (a matrix or named layer)");
+    } else if (want == State::ListTiered || want == State::ListQ8Tiered) {
+        const bool q8 = want == State::ListQ8Tiered;
+        if (q8) {
+            if (int rc = q8_all_arikan(c, spec)) return rc;
+        } else if (c->mixed) {
+            return pfail(BCHK_EINVAL, "tiered state is built for all-Arikan codes (a matrix or named layer)");
+        }
         if (split > c->n) return pfail(BCHK_EINVAL, "split %d out of range (-1, or 1..%d)", split, c->n);
-        c->state = State::ListTiered;
-        if (split < 0) split = auto_split(c, [&](int s) { return (size_t)tiered_layout(c, s).bytes; });
+        c->state = want;
+        if (split < 0) split = auto_split(c, [&](int s) { return (size_t)tiered_layout(c, s, q8).bytes; });
         c->split = split;
         int32_t off[kPolarMaxLayers + 1];
         (void)polar_cw_layout(c->U, off);
         c->cwall = off[c->n] + 1;
         c->cwsplit = split < c->n ? off[split + 1] : c->cwall;
-        c->lds = tiered_layout(c, split).bytes;
+        c->lds = tiered_layout(c, split, q8).bytes;
     } else if (want == State::ListQ8) {
-        for (int j = 0; j < c->n; ++j)
-            if (!c->arikan[j]) {
-                std::istringstream in(spec);
-                std::string name;
-                for (int t = 0; t < 6 + j + 1; ++t) in >> name;  // the header's six numbers, then the layers
-                return pfail(BCHK_EINVAL, "the int8 decoder is built for all-Arikan codes: layer %d is \"%s\"", j,
-                             name.c_str());
-            }
+        if (int rc = q8_all_arikan(c, spec)) return rc;
         c->state = State::ListQ8;
         c->lds = polar_q8_layout(c->U, c->L, c->K, polar_cw_layout(c->U, nullptr)).bytes;
     } else if (c->mixed) {
@@ -838,8 +864,8 @@ static PolarParams polar_list_params(const bchk_polar *c, const PolarIo &io, siz
 int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_t *d_info,
                              uint8_t *d_cw, float *d_metric, int32_t *d_count, void *stream) {
     if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
-    if (c->state == State::ListQ8)
-        return pfail(BCHK_EINVAL, "an int8 context (bchk_polar_create_q8) decodes through bchk_polar_decode_q8_* only");
+    if (c->is_q8())
+        return pfail(BCHK_EINVAL, "an int8 context (bchk_polar_create_q8*) decodes through bchk_polar_decode_q8_* only");
     if (B == 0) return 0;
     if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
     const PolarIo io = polar_io(c, d_llr, d_info, d_cw, d_metric, d_count);
@@ -882,6 +908,7 @@ int bchk_polar_decode_device(bchk_polar *c, const float *d_llr, size_t B, uint8_
     }
     case State::Mixed:
     case State::ListQ8:  // (refused above)
+    case State::ListQ8Tiered:
         break;
     }
     PolarMixedParams m = mixed_params(c->mp);
@@ -936,18 +963,33 @@ int bchk_polar_state_info(const bchk_polar *c, int *split, uint64_t *lds_bytes, 
     return 0;
 }
 
-// The int8 decoder (polar_sclist_q8.hip): d_llr [B][N] int8, the outputs as bchk_polar_decode_device.
+// The int8 decoders (polar_sclist_q8.hip, polar_sclist_q8_tiered.hip): d_llr [B][N] int8, the outputs as
+// bchk_polar_decode_device.
 int bchk_polar_decode_q8_device(bchk_polar *c, const int8_t *d_llr, size_t B, uint8_t *d_info, uint8_t *d_cw,
                                 float *d_metric, int32_t *d_count, void *stream) {
     if (!c || (B && (!d_llr || !d_info || !d_metric || !d_count))) return pfail(BCHK_EINVAL, "NULL argument");
-    if (c->state != State::ListQ8)
-        return pfail(BCHK_EINVAL, "bchk_polar_decode_q8_* take a context of bchk_polar_create_q8 (this one decodes f32 LLRs)");
+    if (!c->is_q8())
+        return pfail(BCHK_EINVAL, "bchk_polar_decode_q8_* take a context of bchk_polar_create_q8* (this one decodes f32 LLRs)");
     if (B == 0) return 0;
     if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    const PolarParams lp = polar_list_params(c, polar_io(c, nullptr, d_info, d_cw, d_metric, d_count), B);
+    const int grid = (int)std::min<size_t>((size_t)c->grid, B);  // tiered: <= the workspaces allocated at create
+    const hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+    if (c->state == State::ListQ8Tiered) {
+        PolarQ8TieredParams q{};
+        q.t.p = lp;
+        q.t.ws = (uint8_t *)c->ws.p;
+        q.t.split = c->split;
+        q.t.cwsplit = c->cwsplit;
+        q.t.cwall = c->cwall;
+        q.llr8 = d_llr;
+        PHIP_TRY(launch_polar_q8_tiered(q, grid, c->lds, s));
+        return 0;
+    }
     PolarQ8Params q{};
-    q.p = polar_list_params(c, polar_io(c, nullptr, d_info, d_cw, d_metric, d_count), B);
+    q.p = lp;
     q.llr8 = d_llr;
-    PHIP_TRY(launch_polar_q8(q, (int)std::min<size_t>((size_t)c->grid, B), c->lds, stream ? (hipStream_t)stream : c->stream));
+    PHIP_TRY(launch_polar_q8(q, grid, c->lds, s));
     return 0;
 }
 
@@ -955,7 +997,7 @@ int bchk_polar_decode_q8_device(bchk_polar *c, const int8_t *d_llr, size_t B, ui
 static int polar_decode_host(bchk_polar *c, const void *llr, size_t elem, size_t B, uint8_t *info, uint8_t *cw,
                              float *metric, int32_t *count) {
     if (!c || (B && (!llr || !info || !metric || !count))) return pfail(BCHK_EINVAL, "NULL argument");
-    if ((elem == 1) != (c->state == State::ListQ8))  // before any copy; the device entries name the reason
+    if ((elem == 1) != c->is_q8())  // before any copy; the device entries name the reason
         return elem == 1 ? bchk_polar_decode_q8_device(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr)
                          : bchk_polar_decode_device(c, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr);
     if (B == 0) return 0;
@@ -1193,9 +1235,9 @@ static int polar_sweep(bchk_polar *c, int channel, double snr_from, double snr_s
     for (int pt = 0; pt < (channel == BCHK_CHANNEL_BSC && points > 0 ? points : 1); ++pt)
         if (int rc = polar_check_channel(channel, snr_from + pt * snr_step)) return rc;
     if (!c || !out) return pfail(BCHK_EINVAL, "NULL argument");
-    if (q8 != (c->state == State::ListQ8))
-        return pfail(BCHK_EINVAL, q8 ? "bchk_polar_sweep_q8_device takes a context of bchk_polar_create_q8"
-                                     : "an int8 context (bchk_polar_create_q8) sweeps through bchk_polar_sweep_q8_device");
+    if (q8 != c->is_q8())
+        return pfail(BCHK_EINVAL, q8 ? "bchk_polar_sweep_q8_device takes a context of bchk_polar_create_q8*"
+                                     : "an int8 context (bchk_polar_create_q8*) sweeps through bchk_polar_sweep_q8_device");
     if (q8)  // scale and qmax, checked as every batch would
         if (int rc = bchk_polar_quantize_device(c, nullptr, 0, scale, qmax, nullptr, nullptr)) return rc;
     if (points <= 0 || max_words == 0 || max_errors == 0)

@@ -11,6 +11,13 @@ LDS bytes and waves per CU of both contexts, and the block error rate of the bes
 (the same words), so that a speed is never read without what it decodes.
 
     python scripts/bench_polar_q8.py
+
+--state tiered_q8 measures the tiered int8 decoder (csrc/polar_sclist_q8_tiered.hip)
+instead: per shape the decoders that exist for it -- tiered f32, LDS q8 where the code fits, tiered
+q8 -- alternate in one run, sampled the same way, and the line carries each one's figures, the
+ratio of tiered q8 to each of the others, and the workspace bytes.
+
+    python scripts/bench_polar_q8.py --state tiered_q8
 """
 import argparse
 import json
@@ -22,6 +29,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "tests"))
 
 SHAPES = ((10, 512, 8, "lds", 1 << 15), (10, 512, 32, "lds", 1 << 14), (11, 1024, 32, "tiered", 1 << 13))
+# --state tiered_q8: (n, K, L, the LDS q8 decoder takes it, B)
+TIERED_SHAPES = ((10, 512, 8, True, 1 << 15), (10, 512, 32, True, 1 << 14), (11, 1024, 32, True, 1 << 13),
+                 (12, 2048, 32, False, 1 << 12), (14, 8192, 8, False, 1 << 12), (14, 8192, 32, False, 1 << 11))
 
 
 def main():
@@ -31,6 +41,9 @@ def main():
     ap.add_argument("--qmax", type=int, default=63)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--state", choices=("lds", "tiered_q8"), default="lds",
+                    help="the q8 decoder measured: the LDS one against f32, or the tiered one against tiered f32 and LDS q8")
+    ap.add_argument("--shapes", type=int, nargs="*", help="indices into the table of shapes (default: all)")
     a = ap.parse_args()
 
     import torch
@@ -40,9 +53,17 @@ def main():
     F = load()
     dev = torch.device("cuda:0")
     cus = torch.cuda.get_device_properties(0).multi_processor_count
-    for n, K, L, state, B in SHAPES:
+    tiered = a.state == "tiered_q8"
+    table = TIERED_SHAPES if tiered else SHAPES
+    for n, K, L, state, B in (table if a.shapes is None else [table[i] for i in a.shapes]):
         spec = arikan_spec(n, K, seed=1)
-        dec = {"f32": F.PolarListDecoder(spec, L, state=state), "q8": F.PolarListDecoder(spec, L, llr="q8")}
+        if tiered:
+            dec = {"tiered_f32": F.PolarListDecoder(spec, L, state="tiered")}
+            if state:
+                dec["lds_q8"] = F.PolarListDecoder(spec, L, llr="q8")
+            dec["q8"] = F.PolarListDecoder(spec, L, llr="q8", state="tiered_q8")
+        else:
+            dec = {"f32": F.PolarListDecoder(spec, L, state=state), "q8": F.PolarListDecoder(spec, L, llr="q8")}
         N = dec["q8"].N
         t_tx = torch.zeros((B, K), dtype=torch.uint8, device=dev)
         t_llr = torch.zeros((B, N), dtype=torch.float32, device=dev)
@@ -55,7 +76,7 @@ def main():
         dec["q8"].generate_device(a.snr, B, t_llr.data_ptr(), t_tx.data_ptr(), seed=1)
         dec["q8"].quantize_device(t_llr.data_ptr(), B * N, t_q.data_ptr(), a.scale, a.qmax)
         dec["q8"].sync()
-        src = {"f32": t_llr, "q8": t_q}
+        src = {kind: t_q if d.llr == "q8" else t_llr for kind, d in dec.items()}
 
         def sample(kind):
             d = dec[kind]
@@ -69,7 +90,7 @@ def main():
             d.sync()
             return B * a.steps / (e0.elapsed_time(e1) * 1e-3)
 
-        fer, rates = {}, {"f32": [], "q8": []}
+        fer, rates = {}, {kind: [] for kind in dec}
         for kind in rates:  # warm-up, and what each decoder makes of these words
             sample(kind)
             fer[kind] = float((t_info[:, 0] != t_tx).any(dim=1).float().mean())
@@ -78,13 +99,20 @@ def main():
                 rates[kind].append(sample(kind))
         row = {"metric": "SC-list decode codewords/s, q8 against f32", "unit": "codewords/s",
                "config": {"workload": f"Arikan polar ({N},{K}), L={L}, Eb/N0={a.snr} dB", "batch": B, "steps": a.steps,
-                          "repeats": a.repeats, "scale": a.scale, "qmax": a.qmax, "f32_state": state}}
+                          "repeats": a.repeats, "scale": a.scale, "qmax": a.qmax,
+                          "f32_state": "tiered" if tiered else state}}
+        if tiered:
+            row["metric"] = "SC-list decode codewords/s, tiered q8 against tiered f32 and LDS q8"
         for kind, d in dec.items():
             si = d.state_info()
             row[kind] = {"median": statistics.median(rates[kind]), "min": min(rates[kind]), "max": max(rates[kind]),
                          "lds_bytes": si["lds_bytes"], "split": si["split"], "waves_per_cu": si["grid"] / cus,
                          "fer_best_path": fer[kind]}
-        row["q8_over_f32"] = row["q8"]["median"] / row["f32"]["median"]
+            if tiered:
+                row[kind]["workspace_bytes"] = si["workspace_bytes"]
+        for kind in dec:
+            if kind != "q8":
+                row[f"q8_over_{kind}"] = row["q8"]["median"] / row[kind]["median"]
         print(json.dumps(row), flush=True)
         for d in dec.values():
             d.close()
