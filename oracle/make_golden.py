@@ -8,6 +8,7 @@ unmodified sources under /root/reference (this container only). The fixtures are
 
     make -C oracle ref && python oracle/make_golden.py            # the Kaneko fixtures
     make -C oracle ref && python oracle/make_golden.py polar      # the polar_ref_* fixtures
+    make -C oracle ref && python oracle/make_golden.py polar-lists  # polar_ref_lists_* alone
 
 The `polar` sub-command needs the product library built as well (kernel matrices come from
 its bchk_kernel_ebch): oracle/_ref/polar_ref is our driver (oracle/polar_ref.cpp) linked with
@@ -154,7 +155,34 @@ POLAR_WORDS = 32
 # it is the largest (tests/short_codes.py: FIXTURES, with_large_rows)
 
 
-def polar():
+# list sizes that are no power of two (tests/test_polar_list_sizes.py): four codes, every L of
+# POLAR_ODD_LISTS each. `polar-lists` writes these files and touches no other.
+POLAR_ODD_LISTS = (3, 5, 6, 7, 12, 24, 31)
+
+
+def polar_lists(code_fixture, emit):
+    import numpy as np
+
+    import dense_codes
+    from polar_lib import arikan_spec
+    from test_polar_mixed import mixed_spec
+
+    emit(code_fixture("lists_arikan_n6", arikan_spec(6, 32, dyn=5, punct=(1, 7), seed=6), (), POLAR_ODD_LISTS,
+                      1.0 + 0.25 * 6, seed=606))
+    # the arikan_n7_ties recipe: LLRs rounded to multiples of 4 (|llr| < 2 becomes 0)
+    emit(code_fixture("lists_arikan_n7_ties", arikan_spec(7, 64, dyn=4, seed=77), (), POLAR_ODD_LISTS, 1.0, seed=707,
+                      llr_map=lambda x: (4.0 * np.round(x / 4.0)).astype(np.float32)))
+    # a matrix kernel, which the reference takes through its trellis processor
+    emit(code_fixture("lists_bch8_A", mixed_spec(("bch8", "A"), 8, 2, (), seed=2 * 11 + 8), ["bch8"], POLAR_ODD_LISTS,
+                      1.0 + 0.25 * 4, seed=808))
+    # 33 constraints live at once: bit 32, in the upper half of the mask. 28 words: with 32 the file
+    # is larger than the largest other polar_ref_* fixture (arikan_n8)
+    name = "dyn_arikan_n7_a33"
+    emit(code_fixture("lists_" + name, dense_codes.spec(name), (), POLAR_ODD_LISTS, dense_codes.SNR[name], seed=909,
+                      words=28))
+
+
+def polar(lists_only=False):
     import tempfile
 
     import numpy as np
@@ -171,8 +199,9 @@ def polar():
     kern = {"k4": KERNELS["k4"], "bch8": F.kernel_ebch(3), "bch16": F.kernel_ebch(4), "bch32": F.kernel_ebch(5),
             "bch32f": F.kernel_field_order(5, F.kernel_ebch(5))}
     os.makedirs(GOLD, exist_ok=True)
-    for p in sum((R.fixture_files(k) for k in ("code", "trellis", "counts", "capacity")), []):
-        os.remove(p)
+    if not lists_only:
+        for p in sum((R.fixture_files(k) for k in ("code", "trellis", "counts", "capacity")), []):
+            os.remove(p)
 
     def emit(fx):
         with tempfile.TemporaryDirectory() as d:
@@ -209,6 +238,9 @@ def polar():
         fx.add("encode", [], [])
         return fx
 
+    polar_lists(code_fixture, emit)
+    if lists_only:
+        return
     for n, K, dyn, punct in POLAR_ARIKAN:
         emit(code_fixture(f"arikan_n{n}", arikan_spec(n, K, dyn=dyn, punct=punct, seed=n), (), POLAR_LISTS,
                           1.0 + 0.25 * n, seed=n * 7))
@@ -339,9 +371,10 @@ def main():
                     "`make -C oracle ref`).",
         epilog="`python oracle/make_golden.py` rewrites the Kaneko fixtures; `python oracle/make_golden.py polar` "
                "rewrites every polar_ref_*.txt.gz (SC-list decoder, encoder, trellis kernel processor, its "
-               "operation counts, the BEC capacity evaluator).")
-    ap.add_argument("what", nargs="?", default="kaneko", choices=["kaneko", "polar"])
-    {"kaneko": kaneko, "polar": polar}[ap.parse_args().what]()
+               "operation counts, the BEC capacity evaluator); `python oracle/make_golden.py polar-lists` writes the "
+               "polar_ref_lists_*.txt.gz among them and leaves the others as they are.")
+    ap.add_argument("what", nargs="?", default="kaneko", choices=["kaneko", "polar", "polar-lists"])
+    {"kaneko": kaneko, "polar": polar, "polar-lists": lambda: polar(lists_only=True)}[ap.parse_args().what]()
 
 
 if __name__ == "__main__":

@@ -66,6 +66,13 @@ class Path:
         return self.S[n][0]
 
 
+# Unfrozen phases decoded since the last STATS.update(...): all of them; those with more than L
+# candidates, where cand[:L] cuts; of these the phases in which a path is killed, another goes on
+# with one bit only and a third is cloned, all at once; and those where the cut falls between the
+# two candidates of one path -- the last candidate kept and the first one dropped are one path's.
+STATS = {"unfrozen": 0, "cut": 0, "three": 0, "split_pair": 0}
+
+
 def decode(spec, llr, L):
     """llr [U] f32 -> (count, info [count][K], codewords [count][U], metrics f32 [count]), the
     list in the library's order. Arikan layers only, nothing shortened or punctured."""
@@ -95,6 +102,12 @@ def decode(spec, llr, L):
         keep = {}
         for r, i in cand[:L]:
             keep.setdefault(i >> 1, []).append(i & 1)
+        STATS["unfrozen"] += 1
+        if len(cand) > L:
+            STATS["cut"] += 1
+            bits = [len(b) for b in keep.values()]
+            STATS["three"] += len(keep) < len(paths) and 1 in bits and 2 in bits
+            STATS["split_pair"] += cand[L - 1][1] >> 1 == cand[L][1] >> 1
         for l in sorted(paths):
             if l not in keep:
                 del paths[l]

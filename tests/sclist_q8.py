@@ -44,7 +44,9 @@ def f_step(a, b):
     return np.where((a < 0) != (b < 0), -m, m).astype(I32)
 
 
-STATS = {"g": 0, "clamped": 0}  # g-step outputs formed, and how many of them saturated
+# g-step outputs formed, and how many of them saturated; decode() adds "split_pair", the unfrozen
+# phases whose cut falls between the two candidates of one path (sclist_plain.STATS)
+STATS = {"g": 0, "clamped": 0}
 
 
 def g_step(a, b, known):
@@ -106,6 +108,8 @@ def decode(spec, q, L):
             cand.append((paths[l].R, 2 * l + hard))
             cand.append((paths[l].R - abs(v[l]), 2 * l + (hard ^ 1)))
         cand.sort(reverse=True)
+        if len(cand) > L:  # as sclist_plain.STATS counts it: the cut falls between one path's two candidates
+            STATS["split_pair"] = STATS.get("split_pair", 0) + (cand[L - 1][1] >> 1 == cand[L][1] >> 1)
         keep = {}
         for r, i in cand[:L]:
             keep.setdefault(i >> 1, []).append(i & 1)

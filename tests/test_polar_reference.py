@@ -14,6 +14,8 @@ oracle/make_golden.py polar`. Format: tests/polar_ref_lib.py.
 
 The dyn_* fixtures (tests/dense_codes.py) are codes with 33 to 64 dynamic freezing constraints
 live at once and constraints of 65 and 130 terms: the upper half of the decoders' 64-bit mask.
+The lists_* fixtures (`oracle/make_golden.py polar-lists`) record four codes at the list sizes
+3, 5, 6, 7, 12, 24 and 31, none a power of two (tests/test_polar_list_sizes.py).
 
 Not pinned (no fixture can exist): kernels of size >= 64, which the reference's trellis
 processor refuses (TrellisKernelProcessor.cpp:71-72) -- the 64 x 64 ordered-statistics path
@@ -81,9 +83,14 @@ def test_the_fixture_set_is_the_one_the_generator_writes():
         "mixed_k4_A", "mixed_bch8_A", "mixed_bch16_A", "mixed_bch32f", "mixed_bch32f_A",
         "short_arikan_n6", "short_bch16_A", "short_arikan_n7",
         "dyn_arikan_n8_a64", "dyn_arikan_n7_a33", "dyn_A_bch16_bch8_a40",
+        "lists_arikan_n6", "lists_arikan_n7_ties", "lists_bch8_A", "lists_dyn_arikan_n7_a33",
         "trellis_bch8", "trellis_bch16", "trellis_bch32", "trellis_bch32f"])
     for p in CODE_FILES:
         fx = fixture(p)
+        if fx.name.startswith("lists"):  # list sizes that are no power of two (tests/test_polar_list_sizes.py)
+            assert fx.list_sizes == [3, 5, 6, 7, 12, 24, 31] and len(fx.info) == 30
+            assert len(fx.llr) == (28 if fx.name == "lists_dyn_arikan_n7_a33" else 32)  # words dropped for the file's size
+            continue
         want = [8] if fx.name.endswith("ties") else [1, 4, 8] if fx.name.startswith(("mixed", "short", "dyn")) else [1, 2, 4, 8, 32]
         assert fx.list_sizes == want and 32 <= len(fx.llr) <= 64 and len(fx.info) == 30
 
