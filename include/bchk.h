@@ -436,7 +436,8 @@ int bchk_polar_generate_device(bchk_polar *pc, double snr_db, size_t B, uint64_t
  * launch, as before. BCHK_EINVAL before any device call, the message naming the argument: an
  * unknown channel; p outside (0, 0.5] or NaN; d_h given for AWGN or the BSC; K = 0 (as
  * bchk_polar_generate_device: the code has no rate). The BEC (commented out at
- * Simulator.cpp:193), block or correlated fading and higher-order modems are not built. */
+ * Simulator.cpp:193) and higher-order modems are not built; block, correlated and Rician fading
+ * are the *_fading* entry points below. */
 int bchk_polar_generate_channel_device(bchk_polar *pc, int channel, double param, size_t B, uint64_t seed,
                                        uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h,
                                        double *d_y, void *stream);
@@ -485,6 +486,40 @@ int bchk_polar_sweep_device(bchk_polar *pc, double snr_from, double snr_step, in
 int bchk_polar_sweep_channel_device(bchk_polar *pc, int channel, double from, double step, int points,
                                     uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
                                     bchk_polar_point *out, double *seconds, uint64_t *words_decoded);
+
+/* ---- The fading models with a parameter (headers/external/Simulation/RayleighBlockChannel.h,
+ * RayleighCorrelatedChannel.h, RacianChannel.h). Common to the three: the stream of
+ * bchk_polar_generate_channel_device (d_info, d_cw and the Gaussian z of an element are those of
+ * every other channel), y = h x + sigma z in double with sigma from the average Eb/N0 snr_db as
+ * for BCHK_CHANNEL_RAYLEIGH (every model has E[h^2] = 1), LLR = (float)(((-2 h) y) / sigma^2),
+ * the receiver knowing h. Word w depends only on (seed, w, kind, param, snr_db). */
+#define BCHK_FADING_BLOCK 0      /* param = the block size S, an integer >= 1: positions [b S,      */
+                                 /* (b + 1) S) of a word share the factor BCHK_CHANNEL_RAYLEIGH     */
+                                 /* gives the block's first element (h = sqrt(-log u(w N + b S))),  */
+                                 /* the last block may be short; S = 1 is BCHK_CHANNEL_RAYLEIGH bit */
+                                 /* for bit, S >= N one factor per word                             */
+#define BCHK_FADING_CORRELATED 1 /* param = rho, 0 <= rho < 1: elements 2 q and 2 q + 1 of a word   */
+                                 /* (QAM symbol q; the last is half filled when N is odd) share     */
+                                 /* h_q = sqrt((a_q^2 + b_q^2) / 2), a and b two unit-variance      */
+                                 /* Gaussian sequences of covariance rho^|i - j|, fresh per word:   */
+                                 /* g_0 = z_0, g_q = fma(rho, g_{q-1}, c z_q), c = sqrt(1 - rho^2)  */
+                                 /* in double, the product rounded before the fma; (z_q of a, z_q   */
+                                 /* of b) = the Box-Muller pair of counter (w low, w high, 0xC022, q) */
+#define BCHK_FADING_RICIAN 2     /* param = the K-factor, finite and >= 0: h = sqrt((v + s z1)^2 +  */
+                                 /* (s z2)^2), v = sqrt(K / (K + 1)), s = sqrt(1 / (2 (K + 1))),    */
+                                 /* (z1, z2) = the Box-Muller pair of counter (w low, w high,       */
+                                 /* 0x21CE, position); K = 0 is Rayleigh fading in law              */
+/* bchk_polar_generate_channel_device, _sweep_channel_device and _sweep_q8_device over a fading
+ * model: (kind, param) choose it, snr_db / the points are average Eb/N0 values in dB. d_h
+ * receives the factors of every kind. BCHK_EINVAL before the context is touched, the message
+ * naming the argument: a kind outside 0..2; a block size below 1 or no integer; rho outside
+ * [0, 1) or NaN; a K-factor negative, NaN or infinite. Everything else as the calls named. */
+int bchk_polar_generate_fading_device(bchk_polar *pc, int kind, double param, double snr_db, size_t B,
+                                      uint64_t seed, uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr,
+                                      double *d_h, double *d_y, void *stream);
+int bchk_polar_sweep_fading_device(bchk_polar *pc, int kind, double param, double snr_from, double snr_step,
+                                   int points, uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                   bchk_polar_point *out, double *seconds, uint64_t *words_decoded);
 
 /* ---- Fixed-point SC-list decoding: int8 LLRs (csrc/polar_sclist_q8.hip). The
  * vendored library's USE_INT8 configuration (SeqConfigOrig.h:186-194, SoftProcessing.cpp:643-1146)
@@ -542,6 +577,11 @@ int bchk_polar_sweep_q8_device(bchk_polar *pc, int channel, double from, double 
                                uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
                                bchk_polar_point *out, double *seconds, uint64_t *words_decoded, float scale,
                                int qmax);
+/* The same on a fading model (bchk_polar_sweep_fading_device). */
+int bchk_polar_sweep_q8_fading_device(bchk_polar *pc, int kind, double param, double snr_from, double snr_step,
+                                      int points, uint64_t max_words, uint64_t max_errors, uint64_t seed,
+                                      size_t batch, bchk_polar_point *out, double *seconds, uint64_t *words_decoded,
+                                      float scale, int qmax);
 
 /* ---- BCH polar-kernel construction and the column-permutation search (root bchCoder.cpp;
  * csrc/kernel_search.hip). Kernels are row-major l x l bytes (0/1). */
@@ -700,6 +740,14 @@ int bchk_polar_genie_run_channel(bchk_polar *pc, int channel, double param, uint
 int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K, int channel, double param,
                                     uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
                                     char *spec, size_t spec_len, size_t *needed);
+/* The same over a fading model: (kind, param) of bchk_polar_generate_fading_device, snr_db the
+ * average Eb/N0. The same refusals, (kind, param) checked first. */
+int bchk_polar_genie_run_fading(bchk_polar *pc, int kind, double param, double snr_db, uint64_t words,
+                                uint64_t seed, uint64_t word0, size_t batch, uint64_t *err, int64_t *soft,
+                                double *seconds);
+int bchk_polar_design_genie_fading(const char *layers, const char *kdir, int K, int kind, double param,
+                                   double snr_db, uint64_t words, uint64_t seed, int device, uint64_t *err,
+                                   int64_t *soft, char *spec, size_t spec_len, size_t *needed);
 
 const char *bchk_last_error(void);
 const char *bchk_version(void);

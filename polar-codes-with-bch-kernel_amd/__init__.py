@@ -11,6 +11,8 @@ Load it by path (the directory name is not an identifier):
     spec = importlib.util.spec_from_file_location("bchk_amd", ".../__init__.py")
 """
 import ctypes as C
+import math
+import numbers
 import os
 import subprocess
 import sys
@@ -49,12 +51,17 @@ EXPORTS = (
     "bchk_polar_design_genie", "bchk_polar_generate_channel_device", "bchk_polar_sweep_channel_device",
     "bchk_polar_genie_run_channel", "bchk_polar_design_genie_channel",
     "bchk_polar_create_q8", "bchk_polar_create_q8_tiered", "bchk_polar_decode_q8_host", "bchk_polar_decode_q8_device",
-    "bchk_polar_quantize_device", "bchk_polar_sweep_q8_device", "bchk_last_error", "bchk_version",
+    "bchk_polar_quantize_device", "bchk_polar_sweep_q8_device",
+    "bchk_polar_generate_fading_device", "bchk_polar_sweep_fading_device", "bchk_polar_genie_run_fading",
+    "bchk_polar_design_genie_fading", "bchk_polar_sweep_q8_fading_device", "bchk_last_error", "bchk_version",
 )
 
 # BCHK_CHANNEL_*: the channels of the polar simulation front-end
 CHANNEL_AWGN, CHANNEL_RAYLEIGH, CHANNEL_BSC = 0, 1, 2
 CHANNELS = {"awgn": CHANNEL_AWGN, "rayleigh": CHANNEL_RAYLEIGH, "bsc": CHANNEL_BSC}
+# BCHK_FADING_*: the fading models with a parameter (FadingChannel)
+FADING_BLOCK, FADING_CORRELATED, FADING_RICIAN = 0, 1, 2
+FADINGS = {"rayleigh_block": FADING_BLOCK, "rayleigh_correlated": FADING_CORRELATED, "rician": FADING_RICIAN}
 
 # struct bchk_polar_point: one Eb/N0 point of PolarListDecoder.sweep_device (on the BSC snr_db holds p)
 POLAR_POINT_DTYPE = np.dtype([("snr_db", "<f8"), ("c", "<u8", (8,))])
@@ -191,6 +198,14 @@ def lib():
     L.bchk_polar_quantize_device.argtypes = [vp, vp, sz, C.c_float, i32, vp, vp]
     L.bchk_polar_sweep_q8_device.argtypes = [vp, i32, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
                                              C.POINTER(u64), C.c_float, i32]
+    L.bchk_polar_generate_fading_device.argtypes = [vp, i32, dbl, dbl, sz, u64, u64, vp, vp, vp, vp, vp, vp]
+    L.bchk_polar_sweep_fading_device.argtypes = [vp, i32, dbl, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
+                                                 C.POINTER(u64)]
+    L.bchk_polar_sweep_q8_fading_device.argtypes = [vp, i32, dbl, dbl, dbl, i32, u64, u64, u64, sz, vp, C.POINTER(dbl),
+                                                    C.POINTER(u64), C.c_float, i32]
+    L.bchk_polar_genie_run_fading.argtypes = [vp, i32, dbl, dbl, u64, u64, u64, sz, vp, vp, C.POINTER(dbl)]
+    L.bchk_polar_design_genie_fading.argtypes = [C.c_char_p, C.c_char_p, i32, i32, dbl, dbl, u64, u64, i32, vp, vp,
+                                                 C.c_char_p, sz, C.POINTER(sz)]
     L.bchk_last_error.restype = C.c_char_p
     L.bchk_version.restype = C.c_char_p
     _lib = L
@@ -206,8 +221,34 @@ def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+class FadingChannel:
+    """A fading model with a parameter, for channel= wherever a channel name is taken:
+    FadingChannel("rayleigh_block", S) (block size S, an integer >= 1), ("rayleigh_correlated", rho)
+    (0 <= rho < 1) or ("rician", K) (K-factor, finite and >= 0). snr_db of the call is the average
+    Eb/N0; include/bchk.h (BCHK_FADING_*) states the models."""
+
+    def __init__(self, kind, param):
+        if not isinstance(kind, str) or kind not in FADINGS:
+            raise ValueError(f"kind must be one of {sorted(FADINGS)}, not {kind!r}")
+        if isinstance(param, bool) or not isinstance(param, numbers.Real):  # no strings, no truth values
+            raise ValueError(f"{kind}: the parameter must be a real number, not {param!r}")
+        value = float(param)
+        if kind == "rayleigh_block" and not (math.isfinite(value) and value >= 1.0 and value == math.floor(value)):
+            raise ValueError(f"rayleigh_block: the block size must be an integer >= 1, not {param!r}")
+        if kind == "rayleigh_correlated" and not 0.0 <= value < 1.0:
+            raise ValueError(f"rayleigh_correlated: rho must lie in [0, 1), not {param!r}")
+        if kind == "rician" and not 0.0 <= value < float("inf"):
+            raise ValueError(f"rician: the K-factor must be finite and >= 0, not {param!r}")
+        self.kind, self.param = kind, value
+
+    def __repr__(self):
+        return f"FadingChannel({self.kind!r}, {self.param!r})"
+
+
 def _channel(channel):
-    """BCHK_CHANNEL_* of "awgn" | "rayleigh" | "bsc"."""
+    """BCHK_CHANNEL_* of "awgn" | "rayleigh" | "bsc"; a FadingChannel gives its (BCHK_FADING_*, param)."""
+    if isinstance(channel, FadingChannel):
+        return FADINGS[channel.kind], channel.param
     try:
         return CHANNELS[channel]
     except (KeyError, TypeError):
@@ -580,10 +621,13 @@ class PolarListDecoder:
         "rayleigh" (real Rayleigh fading known to the receiver, snr_db the average Eb/N0) or "bsc"
         (snr_db is then the crossover probability p, LLRs +-2); information bits and codewords do
         not depend on it. d_h and d_y [B][N] f64, where given, receive the fading factor (Rayleigh
-        only) and the channel output."""
-        _check(lib().bchk_polar_generate_channel_device(self._h, _channel(channel), snr_db, B, seed, word0,
-                                                        d_info or None, d_cw or None, d_llr or None, d_h or None,
-                                                        d_y or None, stream))
+        and the FadingChannel models) and the channel output. channel may also be a FadingChannel."""
+        chan = _channel(channel)
+        tail = (snr_db, B, seed, word0, d_info or None, d_cw or None, d_llr or None, d_h or None, d_y or None, stream)
+        if isinstance(chan, tuple):
+            _check(lib().bchk_polar_generate_fading_device(self._h, *chan, *tail))
+        else:
+            _check(lib().bchk_polar_generate_channel_device(self._h, chan, *tail))
 
     def count_device(self, d_info_tx, d_cw_tx, d_llr, d_info, d_cw, d_count, B, d_out8, d_flags=None,
                      stream=None):
@@ -607,12 +651,14 @@ class PolarListDecoder:
                              else "scale applies to a q8 decoder only")
         out = np.zeros(max(points, 0), POLAR_POINT_DTYPE)
         secs, words = C.c_double(0.0), C.c_uint64(0)
-        args = (self._h, chan, snr_from, snr_step, points, max_words, max_errors, seed, batch,
+        fading = isinstance(chan, tuple)
+        args = (self._h, *(chan if fading else (chan,)), snr_from, snr_step, points, max_words, max_errors, seed, batch,
                 _p(out) if points > 0 else None, C.byref(secs), C.byref(words))
+        L = lib()
         if self.llr == "q8":
-            _check(lib().bchk_polar_sweep_q8_device(*args, scale, qmax))
+            _check((L.bchk_polar_sweep_q8_fading_device if fading else L.bchk_polar_sweep_q8_device)(*args, scale, qmax))
         else:
-            _check(lib().bchk_polar_sweep_channel_device(*args))
+            _check((L.bchk_polar_sweep_fading_device if fading else L.bchk_polar_sweep_channel_device)(*args))
         return [(float(r["snr_db"]), [int(v) for v in r["c"]]) for r in out], secs.value, words.value
 
     def genie_device(self, d_info_tx, d_llr, B, d_err, d_soft, d_dec_llr=None, d_u=None, stream=None):
@@ -630,8 +676,12 @@ class PolarListDecoder:
         err = np.zeros(self.U, np.uint64)
         soft = np.zeros(self.U, np.int64)
         secs = C.c_double(0.0)
-        _check(lib().bchk_polar_genie_run_channel(self._h, _channel(channel), snr_db, words, seed, word0, batch,
-                                                  _p(err), _p(soft), C.byref(secs)))
+        chan = _channel(channel)
+        tail = (snr_db, words, seed, word0, batch, _p(err), _p(soft), C.byref(secs))
+        if isinstance(chan, tuple):
+            _check(lib().bchk_polar_genie_run_fading(self._h, *chan, *tail))
+        else:
+            _check(lib().bchk_polar_genie_run_channel(self._h, chan, *tail))
         return err, soft, secs.value
 
     def sync(self):
@@ -853,15 +903,20 @@ def design_genie(layers, K, snr_db, words, kernel_dir=None, seed=1, device=0, ch
     error counts over `words` words of the stream `seed` at Eb/N0 snr_db (ties: the larger soft sum,
     then the higher index) -> (spec text for PolarListDecoder, err [U] u64, soft [U] i64).
     Layers may be "A", matrix files, and the named kernels "G" and "A5". channel = "awgn",
-    "rayleigh" or "bsc" (snr_db is then the crossover probability): the design is for that channel."""
+    "rayleigh", "bsc" (snr_db is then the crossover probability) or a FadingChannel: the design is
+    for that channel."""
     line = layers if isinstance(layers, str) else " ".join(layers)
     err = np.zeros(16384, np.uint64)
     soft = np.zeros(16384, np.int64)
     buf = C.create_string_buffer(64 + len(line) + 8 * 16384)
     needed = C.c_size_t()
-    _check(lib().bchk_polar_design_genie_channel(line.encode(), kernel_dir.encode() if kernel_dir else None, K,
-                                                 _channel(channel), snr_db, words, seed, device, _p(err), _p(soft),
-                                                 buf, len(buf), C.byref(needed)))
+    chan = _channel(channel)
+    head = (line.encode(), kernel_dir.encode() if kernel_dir else None, K)
+    tail = (snr_db, words, seed, device, _p(err), _p(soft), buf, len(buf), C.byref(needed))
+    if isinstance(chan, tuple):
+        _check(lib().bchk_polar_design_genie_fading(*head, *chan, *tail))
+    else:
+        _check(lib().bchk_polar_design_genie_channel(*head, chan, *tail))
     spec = buf.value.decode()
     U = int(spec.split()[0])
     return spec, err[:U].copy(), soft[:U].copy()

@@ -19,9 +19,16 @@
 //                                               even, of (2, 3) when G is odd: (a 2^21 + (b >> 11)
 //                                               + 1) 2^-53 in (0, 1] for the word pair (a, b)
 //   BEC pattern draw of sample s, weight w:     (s low, s high, w, 0xBEC00000 + attempt)
-// Word 2 tells the four apart: 0xFFFFFFFF, 0x5EED, 0xFAD1, and a weight of at most 64.
-// tests/philox_lib.py restates all of it but u(G), which tests/channel_lib.py restates;
-// tests/test_stream_reference.py and tests/test_polar_channels.py compare.
+//   correlated fading, QAM symbol q of word w (polar stream): the Box-Muller pair of counter
+//                                               (w low, w high, 0xC022, q): element 0 drives the
+//                                               sequence a, element 1 the sequence b
+//   Rician fading, position i of word w (polar stream): the Box-Muller pair (z1, z2) of counter
+//                                               (w low, w high, 0x21CE, i)
+// Word 2 tells the six apart: 0xFFFFFFFF, 0x5EED, 0xFAD1, 0xC022, 0x21CE, and a weight of at
+// most 64.
+// tests/philox_lib.py restates all of it but u(G), which tests/channel_lib.py restates, and the
+// two fading pairs, which tests/fading_lib.py restates; tests/test_stream_reference.py,
+// tests/test_polar_channels.py and tests/test_polar_fading.py compare.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,15 +59,23 @@ __device__ __forceinline__ double unit53(uint32_t a, uint32_t b) {
     return ((double)(v & ((1ull << 53) - 1ull)) + 1.0) * 0x1p-53;
 }
 
-// the standard normal pair of noise counter `pair` (elements 2 pair and 2 pair + 1)
-__device__ __forceinline__ void normal_pair(uint64_t pair, uint32_t k0, uint32_t k1, double z[2]) {
-    const U4 r = philox(U4{(uint32_t)pair, (uint32_t)(pair >> 32), 0x5EEDu, 0u}, k0, k1);
+constexpr uint32_t kTagCorrelated = 0xC022u, kTagRician = 0x21CEu;
+
+// the standard normal pair (Box-Muller) of counter (c low, c high, tag, c3)
+__device__ __forceinline__ void normal_pair_of(uint64_t c, uint32_t tag, uint32_t c3, uint32_t k0, uint32_t k1,
+                                               double z[2]) {
+    const U4 r = philox(U4{(uint32_t)c, (uint32_t)(c >> 32), tag, c3}, k0, k1);
     const double u1 = unit53(r.x, r.y), u2 = unit53(r.z, r.w);
     const double rad = sqrt(-2.0 * log(u1));
     double sn, cs;
     sincospi(2.0 * u2, &sn, &cs);
     z[0] = rad * cs;
     z[1] = rad * sn;
+}
+
+// the standard normal pair of noise counter `pair` (elements 2 pair and 2 pair + 1)
+__device__ __forceinline__ void normal_pair(uint64_t pair, uint32_t k0, uint32_t k1, double z[2]) {
+    normal_pair_of(pair, 0x5EEDu, 0u, k0, k1, z);
 }
 
 // the fading / crossover uniforms of counter `pair` (elements 2 pair and 2 pair + 1)

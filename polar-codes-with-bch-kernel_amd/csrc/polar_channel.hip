@@ -20,7 +20,11 @@
 // position of the stream takes one of the Box-Muller pair of counter G / 2. The kernel is a
 // template over the channel: the Rayleigh and BSC instantiations draw one more uniform per
 // element (the pair of counter G / 2 under the tag 0xFAD1) in the same loop, and every
-// instantiation stores one LLR per symbol, h and y as doubles beside it when asked.
+// instantiation stores one LLR per symbol, h and y as doubles beside it when asked. Three more
+// instantiations are the vendored library's fading models with a parameter
+// (headers/external/Simulation/RayleighBlockChannel.h, RayleighCorrelatedChannel.h,
+// RacianChannel.h; polar_device.h states them): block and Rician fading element-wise in the same
+// loop, correlated fading in gen_correlated, whose recursion along the word runs across the lanes.
 //
 // polar_count_kernel: one wave per decoded word, CSimulator::Iterate's counters
 // (Simulator.cpp:201-318); CurCorr and MLCorr of an errored word are summed in double in
@@ -37,6 +41,73 @@ namespace {
 
 using penc::ubit;
 using plist::wsync;
+
+// One element of a fading channel: y = h x + sigma z (Simulator.cpp:185-186) and the LLR
+// (Modem.h:78 with the fading factor), evaluated as ((-2 h) y) / var.
+__device__ __forceinline__ void store_faded(const PolarGenParams &p, double fade, double x, double z, int el,
+                                            float *llr, double *fout, double *yout) {
+    const double y = fade * x + p.sigma * z;
+    llr[el] = (float)(-2.0 * fade * y / p.var);
+    if (fout) fout[el] = fade;
+    if (yout) yout[el] = y;
+}
+
+// v of lane j (wave-uniform)
+__device__ __forceinline__ double lane_f64(double v, int j) {
+    const long long b = __double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)b, j);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((unsigned long long)b >> 32), j);
+    return __longlong_as_double((long long)((uint64_t)lo | ((uint64_t)hi << 32)));
+}
+
+// Correlated Rayleigh fading of one word (RayleighCorrelatedChannel.h:97-137): QAM symbol q =
+// elements 2 q, 2 q + 1 of the word, 64 symbols at a time. Every lane draws the (z_a, z_b) of its
+// symbol; the two AR(1) recursions (the Cholesky factor of rho^|i-j|) then walk the lanes in
+// order, g carried in a register across the chunks -- the sequential recursion bit for bit, and
+// nothing of it in LDS -- and every lane keeps the pair of its own step.
+__device__ __forceinline__ void gen_correlated(const PolarGenParams &p, const uint32_t *c32, uint64_t word, int lane,
+                                               float *llr, double *fout, double *yout) {
+    const int N = p.t.N, nq = (N + 1) >> 1;
+    const uint64_t ebase = word * (uint64_t)N;
+    double ga = 0.0, gb = 0.0;  // wave-uniform; fma(rho, 0, z_0) = z_0
+    for (int q0 = 0; q0 < nq; q0 += 64) {
+        const int q = q0 + lane;
+        double in[2] = {0.0, 0.0};
+        if (q < nq) {
+            normal_pair_of(word, kTagCorrelated, (uint32_t)q, p.seed_lo, p.seed_hi, in);
+            if (q) {  // c z_q, rounded before the fma
+                in[0] = p.f1 * in[0];
+                in[1] = p.f1 * in[1];
+            }
+        }
+        const int m = nq - q0 < 64 ? nq - q0 : 64;
+        double a = 0.0, b = 0.0;
+        for (int j = 0; j < m; ++j) {
+            ga = fma(p.f0, ga, lane_f64(in[0], j));
+            gb = fma(p.f0, gb, lane_f64(in[1], j));
+            if (j == lane) {
+                a = ga;
+                b = gb;
+            }
+        }
+        if (q < nq) {
+            const double fade = sqrt((a * a + b * b) / 2.0);
+            // z of the AWGN stream: flat elements g0 and g0 + 1 share a pair where g0 is even
+            const uint64_t g0 = ebase + 2ull * (uint64_t)q;
+            double z0[2], z1[2] = {0.0, 0.0};
+            normal_pair(g0 >> 1, p.seed_lo, p.seed_hi, z0);
+            if (g0 & 1ull) normal_pair((g0 >> 1) + 1ull, p.seed_lo, p.seed_hi, z1);  // wave-uniform
+            const double zz[2] = {(g0 & 1ull) ? z0[1] : z0[0], (g0 & 1ull) ? z1[0] : z0[1]};
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                const int el = 2 * q + h;
+                if (el >= N) continue;
+                const double x = ubit(c32, p.t.cwpos[el]) ? 1.0 : -1.0;
+                store_faded(p, fade, x, zz[h], el, llr, fout, yout);
+            }
+        }
+    }
+}
 
 template <int CH>
 __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGenParams p) {
@@ -123,33 +194,47 @@ __global__ void __launch_bounds__(64 * kPolarChanWaves) polar_gen_kernel(PolarGe
             // elements 2 p and 2 p + 1 (a pair may straddle two words: each wave computes it),
             // and so does the pair of fading / crossover uniforms
             float *llr = p.llr + w * (uint64_t)N;
-            double *fout = CH == kPolarChanRayleigh && p.fade ? p.fade + w * (uint64_t)N : nullptr;
+            double *fout = (CH == kPolarChanRayleigh || CH >= kPolarChanFading) && p.fade ? p.fade + w * (uint64_t)N
+                                                                                           : nullptr;
             double *yout = p.y ? p.y + w * (uint64_t)N : nullptr;
             const uint64_t ebase = word * (uint64_t)N;
             const uint64_t p0 = ebase >> 1, pend = (ebase + (uint64_t)N + 1) >> 1;
-            for (uint64_t pr = p0 + (uint64_t)lane; pr < pend; pr += 64) {
-                double z[2], u[2];
-                if (CH != kPolarChanBsc) normal_pair(pr, p.seed_lo, p.seed_hi, z);
-                if (CH != kPolarChanAwgn) unit_pair(pr, p.seed_lo, p.seed_hi, u);
+            if constexpr (CH == kPolarChanCorrelated) {  // the recursion along the word: a loop of its own
+                gen_correlated(p, c32, word, lane, llr, fout, yout);
+            } else {
+                for (uint64_t pr = p0 + (uint64_t)lane; pr < pend; pr += 64) {
+                    double z[2], u[2];
+                    if (CH != kPolarChanBsc) normal_pair(pr, p.seed_lo, p.seed_hi, z);
+                    if (CH == kPolarChanRayleigh || CH == kPolarChanBsc) unit_pair(pr, p.seed_lo, p.seed_hi, u);
 #pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int64_t el = (int64_t)(2 * pr + (uint64_t)h) - (int64_t)ebase;  // within the word
-                    if (el < 0 || el >= (int64_t)N) continue;
-                    const double x = ubit(c32, t.cwpos[el]) ? 1.0 : -1.0;  // Modem.h:64
-                    if constexpr (CH == kPolarChanAwgn) {
-                        const double y = x + p.sigma * z[h];
-                        llr[el] = (float)(-2.0 * y / p.var);  // Modem.h:78
-                        if (yout) yout[el] = y;
-                    } else if constexpr (CH == kPolarChanRayleigh) {
-                        const double fade = sqrt(-log(u[h]));  // gsl_ran_rayleigh(1 / sqrt 2), Simulator.cpp:184
-                        const double y = fade * x + p.sigma * z[h];  // :185-186
-                        llr[el] = (float)(-2.0 * fade * y / p.var);  // Modem.h:78 with the fading factor
-                        if (fout) fout[el] = fade;
-                        if (yout) yout[el] = y;
-                    } else {
-                        const double y = u[h] > p.cross ? x : -x;  // :189-190
-                        llr[el] = (float)(-2.0 * y);  // noise variance 1 (:114)
-                        if (yout) yout[el] = y;
+                    for (int h = 0; h < 2; ++h) {
+                        const int64_t el = (int64_t)(2 * pr + (uint64_t)h) - (int64_t)ebase;  // within the word
+                        if (el < 0 || el >= (int64_t)N) continue;
+                        const double x = ubit(c32, t.cwpos[el]) ? 1.0 : -1.0;  // Modem.h:64
+                        if constexpr (CH == kPolarChanAwgn) {
+                            const double y = x + p.sigma * z[h];
+                            llr[el] = (float)(-2.0 * y / p.var);  // Modem.h:78
+                            if (yout) yout[el] = y;
+                        } else if constexpr (CH == kPolarChanRayleigh) {
+                            // gsl_ran_rayleigh(1 / sqrt 2), Simulator.cpp:184-186
+                            store_faded(p, sqrt(-log(u[h])), x, z[h], (int)el, llr, fout, yout);
+                        } else if constexpr (CH == kPolarChanBlock) {
+                            // the Rayleigh factor of the first element of the block (RayleighBlockChannel.h:61-70)
+                            const uint64_t gb = ebase + (uint64_t)((int)el / p.fblock) * (uint64_t)p.fblock;
+                            double ub[2];
+                            unit_pair(gb >> 1, p.seed_lo, p.seed_hi, ub);
+                            store_faded(p, sqrt(-log(ub[gb & 1ull])), x, z[h], (int)el, llr, fout, yout);
+                        } else if constexpr (CH == kPolarChanRician) {
+                            // Rice(v, s): the line-of-sight part v on the first of two N(0, s^2) components
+                            double r[2];
+                            normal_pair_of(word, kTagRician, (uint32_t)el, p.seed_lo, p.seed_hi, r);
+                            const double re = p.f0 + p.f1 * r[0], im = p.f1 * r[1];
+                            store_faded(p, sqrt(re * re + im * im), x, z[h], (int)el, llr, fout, yout);
+                        } else {
+                            const double y = u[h] > p.cross ? x : -x;  // :189-190
+                            llr[el] = (float)(-2.0 * y);  // noise variance 1 (:114)
+                            if (yout) yout[el] = y;
+                        }
                     }
                 }
             }
@@ -258,6 +343,12 @@ hipError_t launch_polar_gen(const PolarGenParams &p, hipStream_t s) {
         hipLaunchKernelGGL(polar_gen_kernel<kPolarChanRayleigh>, grid, block, lds, s, p);
     else if (p.gen && p.channel == kPolarChanBsc)
         hipLaunchKernelGGL(polar_gen_kernel<kPolarChanBsc>, grid, block, lds, s, p);
+    else if (p.gen && p.channel == kPolarChanBlock)
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanBlock>, grid, block, lds, s, p);
+    else if (p.gen && p.channel == kPolarChanCorrelated)
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanCorrelated>, grid, block, lds, s, p);
+    else if (p.gen && p.channel == kPolarChanRician)
+        hipLaunchKernelGGL(polar_gen_kernel<kPolarChanRician>, grid, block, lds, s, p);
     else  // AWGN, and every encode
         hipLaunchKernelGGL(polar_gen_kernel<kPolarChanAwgn>, grid, block, lds, s, p);
     return hipGetLastError();

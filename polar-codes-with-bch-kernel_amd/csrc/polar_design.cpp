@@ -3,7 +3,7 @@
 // capacity evaluation of a kernel's BEC polarisation table, the kernel-file writer that stores
 // that table where the reference reads it, and the layer-by-layer capacity recursion that
 // picks the frozen set of a code specification. Also the Monte-Carlo design over a simulated
-// channel (bchk_polar_design_genie, bchk_polar_design_genie_channel): the frozen set ranked by
+// channel (bchk_polar_design_genie, _channel, _fading): the frozen set ranked by
 // the genie-aided error statistics of bchk_polar_genie_run_channel (polar_host.cpp,
 // polar_genie.hip).
 //
@@ -32,6 +32,7 @@
 namespace bchk {
 void set_last_error(const char *msg);  // bchk_host.cpp
 int polar_check_channel(int channel, double param);  // polar_host.cpp
+int polar_check_fading(int kind, double param);
 }
 
 namespace {
@@ -312,12 +313,11 @@ int bchk_polar_design_bec(const char *layers, const char *kdir, int K, double ca
 // (bchk_polar_genie_run_channel) over `words` words of the stream `seed` over `channel` at
 // `param`, decoded as the code with the lowest indices frozen (the rate K / U fixes the noise
 // deviation; the statistics do not depend on the frozen set, every earlier symbol being fed
-// back true).
-int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K, int channel, double param,
-                                    uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
-                                    char *spec, size_t spec_len, size_t *needed) {
-    if (needed) *needed = 0;
-    if (int rc = bchk::polar_check_channel(channel, param)) return rc;
+// back true). fading: (channel, fpar) = (kind, param) of a fading model, param its Eb/N0; both
+// checked by the caller.
+static int design_genie(const char *layers, const char *kdir, int K, bool fading, int channel, double param,
+                        double fpar, uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
+                        char *spec, size_t spec_len, size_t *needed) {
     if (!layers || !needed) return dfail(BCHK_EINVAL, "NULL argument");
     if (words == 0 || words > (1ull << 31)) return dfail(BCHK_EINVAL, "words must be 1..2^31");
     std::istringstream in(layers);
@@ -354,7 +354,10 @@ int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K,
     if (int rc = bchk_polar_create_kdir(base.c_str(), kdir, 1, device, &pc)) return rc;
     std::vector<uint64_t> e(U);
     std::vector<int64_t> s(U);
-    const int rc = bchk_polar_genie_run_channel(pc, channel, param, words, seed, 0, 0, e.data(), s.data(), nullptr);
+    const int rc = fading ? bchk_polar_genie_run_fading(pc, channel, fpar, param, words, seed, 0, 0, e.data(), s.data(),
+                                                        nullptr)
+                          : bchk_polar_genie_run_channel(pc, channel, param, words, seed, 0, 0, e.data(), s.data(),
+                                                         nullptr);
     bchk_polar_destroy(pc);
     if (rc) return rc;
     // i is better than j: fewer errors, then the larger soft sum, then the higher index
@@ -375,6 +378,24 @@ int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K,
     if (err) std::copy(e.begin(), e.end(), err);
     if (soft) std::copy(s.begin(), s.end(), soft);
     return BCHK_OK;
+}
+
+int bchk_polar_design_genie_channel(const char *layers, const char *kdir, int K, int channel, double param,
+                                    uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft,
+                                    char *spec, size_t spec_len, size_t *needed) {
+    if (needed) *needed = 0;
+    if (int rc = bchk::polar_check_channel(channel, param)) return rc;
+    return design_genie(layers, kdir, K, false, channel, param, 0.0, words, seed, device, err, soft, spec, spec_len,
+                        needed);
+}
+
+int bchk_polar_design_genie_fading(const char *layers, const char *kdir, int K, int kind, double param, double snr_db,
+                                   uint64_t words, uint64_t seed, int device, uint64_t *err, int64_t *soft, char *spec,
+                                   size_t spec_len, size_t *needed) {
+    if (needed) *needed = 0;
+    if (int rc = bchk::polar_check_fading(kind, param)) return rc;
+    return design_genie(layers, kdir, K, true, kind, snr_db, param, words, seed, device, err, soft, spec, spec_len,
+                        needed);
 }
 
 int bchk_polar_design_genie(const char *layers, const char *kdir, int K, double snr_db, uint64_t words, uint64_t seed,

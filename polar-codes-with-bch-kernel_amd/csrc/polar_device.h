@@ -203,6 +203,16 @@ struct PolarEncTables {
 // (BCHK_CHANNEL_*, include/bchk.h) chooses the kernel's instantiation: Rayleigh fades x by
 // h = sqrt(-log u) and weighs the LLR with it, the BSC flips x where u <= cross and stores -2 y.
 constexpr int kPolarChanAwgn = 0, kPolarChanRayleigh = 1, kPolarChanBsc = 2;
+// The fading models with a parameter (BCHK_FADING_* + kPolarChanFading, the *_fading entry
+// points): y = h x + sigma z and LLR = ((-2 h) y) / var as on the Rayleigh channel, with
+//   block:      h = the Rayleigh factor of the first element of the position's block of fblock
+//   correlated: h_q = sqrt((a_q^2 + b_q^2) / 2) on elements 2 q, 2 q + 1 of the word; a, b two
+//               AR(1) sequences g_0 = z_0, g_q = fma(f0, g_{q-1}, f1 z_q) over the normal pairs
+//               of counter (word low, word high, kTagCorrelated, q): f0 = rho, f1 = sqrt(1 - rho^2)
+//   Rician:     h = sqrt((f0 + f1 z1)^2 + (f1 z2)^2), (z1, z2) the normal pair of counter (word
+//               low, word high, kTagRician, position): f0 = v, f1 = s
+constexpr int kPolarChanFading = 3;
+constexpr int kPolarChanBlock = 3, kPolarChanCorrelated = 4, kPolarChanRician = 5;
 struct PolarGenParams {
     PolarEncTables t;
     const uint8_t *info_in;  // [B][K] (encode)
@@ -216,7 +226,9 @@ struct PolarGenParams {
     double sigma, var;
     int32_t channel;         // kPolarChan*
     double cross;            // the BSC's crossover probability
-    double *fade;            // [B][N] h (Rayleigh; may be null)
+    int32_t fblock;          // block fading: the block size, 1 .. N
+    double f0, f1;           // correlated and Rician fading: see above
+    double *fade;            // [B][N] h (Rayleigh and the fading models; may be null)
     double *y;               // [B][N] the channel output before the demodulator (may be null)
 };
 // CSimulator::Iterate's counters of one decoded batch (Simulator.cpp:201-318), added into

@@ -52,7 +52,8 @@ hipError_t launch_polar_genie_sum(const float *dec_llr, const uint8_t *u, uint32
                                   int64_t *soft, hipStream_t s);
 const void *polar_genie_kernel_ptr();
 void set_last_error(const char *msg);  // bchk_host.cpp: the message bchk_last_error returns
-int polar_check_channel(int channel, double param);  // below; polar_design.cpp calls it too
+int polar_check_channel(int channel, double param);  // below; polar_design.cpp calls both too
+int polar_check_fading(int kind, double param);
 }  // namespace bchk
 
 namespace {
@@ -1119,6 +1120,10 @@ size_t cut_at_error(const std::vector<uint8_t> &flags, size_t nb, uint64_t need)
 
 static_assert(BCHK_CHANNEL_AWGN == kPolarChanAwgn && BCHK_CHANNEL_RAYLEIGH == kPolarChanRayleigh &&
                   BCHK_CHANNEL_BSC == kPolarChanBsc, "the kernel's channel ids are the ABI's");
+static_assert(kPolarChanFading + BCHK_FADING_BLOCK == kPolarChanBlock &&
+                  kPolarChanFading + BCHK_FADING_CORRELATED == kPolarChanCorrelated &&
+                  kPolarChanFading + BCHK_FADING_RICIAN == kPolarChanRician,
+              "the kernel's fading models follow its channels in the ABI's order");
 
 }  // namespace
 
@@ -1134,7 +1139,65 @@ int polar_check_channel(int channel, double param) {
     return 0;
 }
 
+// (kind, param) of the bchk_polar_*_fading* entry points, checked before anything else of a call.
+int polar_check_fading(int kind, double param) {
+    if (kind != BCHK_FADING_BLOCK && kind != BCHK_FADING_CORRELATED && kind != BCHK_FADING_RICIAN)
+        return pfail(BCHK_EINVAL, "kind %d unknown (BCHK_FADING_BLOCK, _CORRELATED or _RICIAN)", kind);
+    if (kind == BCHK_FADING_BLOCK && !(param >= 1.0 && param == floor(param) && std::isfinite(param)))  // NaN fails
+        return pfail(BCHK_EINVAL, "block size %g: an integer of at least 1", param);
+    if (kind == BCHK_FADING_CORRELATED && !(param >= 0.0 && param < 1.0))
+        return pfail(BCHK_EINVAL, "rho = %g: the correlation coefficient lies in [0, 1)", param);
+    if (kind == BCHK_FADING_RICIAN && !(param >= 0.0 && std::isfinite(param)))
+        return pfail(BCHK_EINVAL, "K-factor %g: finite and not negative", param);
+    return 0;
+}
+
 }  // namespace bchk
+
+// Words [word0, word0 + B) of the stream `seed` over the kernel's channel `chan` (kPolarChan*,
+// checked by the caller): param = Eb/N0 in dB, on the BSC the crossover probability; fpar = the
+// parameter of a fading model.
+static int polar_generate(bchk_polar *c, int chan, double param, double fpar, size_t B, uint64_t seed, uint64_t word0,
+                          uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h, double *d_y, void *stream) {
+    if (d_h && chan != kPolarChanRayleigh && chan < kPolarChanFading)
+        return pfail(BCHK_EINVAL, "d_h must be NULL: channel %d has no fading factor", chan);
+    if (!c || (B && !d_llr)) return pfail(BCHK_EINVAL, "NULL argument");
+    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
+    if (B == 0) return 0;
+    if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
+    PolarGenParams p{};
+    p.t = enc_tables(c);
+    p.info = d_info;
+    p.cw = d_cw;
+    p.llr = d_llr;
+    p.fade = d_h;
+    p.y = d_y;
+    p.word0 = word0;
+    p.B = (uint32_t)B;
+    p.seed_lo = (uint32_t)seed;
+    p.seed_hi = (uint32_t)(seed >> 32);
+    p.gen = 1;
+    p.channel = chan;
+    p.fblock = 1;
+    if (chan == kPolarChanBsc) {
+        p.cross = param;
+        p.sigma = p.var = 1.0;
+    } else {
+        p.sigma = sqrt(0.5 * pow(10, -param / 10) * c->N / c->K);
+        p.var = p.sigma * p.sigma;  // CModem::SetNoiseVariance (Simulator.cpp:109)
+    }
+    if (chan == kPolarChanBlock) {  // a block of N or more is the whole word
+        p.fblock = fpar < (double)c->N ? (int32_t)fpar : c->N;
+    } else if (chan == kPolarChanCorrelated) {
+        p.f0 = fpar;
+        p.f1 = sqrt(1.0 - fpar * fpar);
+    } else if (chan == kPolarChanRician) {  // Omega = 2 s^2 + v^2 = 1, K = v^2 / (2 s^2)
+        p.f0 = sqrt(fpar / (fpar + 1.0));
+        p.f1 = sqrt(1.0 / (2.0 * (fpar + 1.0)));
+    }
+    PHIP_TRY(launch_polar_gen(p, stream ? (hipStream_t)stream : c->stream));
+    return 0;
+}
 
 extern "C" {
 
@@ -1160,34 +1223,17 @@ int bchk_polar_generate_channel_device(bchk_polar *c, int channel, double param,
                                        uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h,
                                        double *d_y, void *stream) {
     if (int rc = polar_check_channel(channel, param)) return rc;
-    if (d_h && channel != BCHK_CHANNEL_RAYLEIGH)
-        return pfail(BCHK_EINVAL, "d_h must be NULL: channel %d has no fading factor", channel);
-    if (!c || (B && !d_llr)) return pfail(BCHK_EINVAL, "NULL argument");
-    if (B > 0xFFFFFFFFull) return pfail(BCHK_EINVAL, "batch too large");
-    if (B == 0) return 0;
-    if (c->K <= 0) return pfail(BCHK_EINVAL, "a code of dimension 0 has no Eb/N0");
-    PolarGenParams p{};
-    p.t = enc_tables(c);
-    p.info = d_info;
-    p.cw = d_cw;
-    p.llr = d_llr;
-    p.fade = d_h;
-    p.y = d_y;
-    p.word0 = word0;
-    p.B = (uint32_t)B;
-    p.seed_lo = (uint32_t)seed;
-    p.seed_hi = (uint32_t)(seed >> 32);
-    p.gen = 1;
-    p.channel = channel;
-    if (channel == BCHK_CHANNEL_BSC) {
-        p.cross = param;
-        p.sigma = p.var = 1.0;
-    } else {
-        p.sigma = sqrt(0.5 * pow(10, -param / 10) * c->N / c->K);
-        p.var = p.sigma * p.sigma;  // CModem::SetNoiseVariance (Simulator.cpp:109)
-    }
-    PHIP_TRY(launch_polar_gen(p, stream ? (hipStream_t)stream : c->stream));
-    return 0;
+    return polar_generate(c, channel, param, 0.0, B, seed, word0, d_info, d_cw, d_llr, d_h, d_y, stream);
+}
+
+// The same stream over a fading model with a parameter (polar_device.h; include/bchk.h):
+// snr_db = the average Eb/N0, every model having E[h^2] = 1.
+int bchk_polar_generate_fading_device(bchk_polar *c, int kind, double param, double snr_db, size_t B, uint64_t seed,
+                                      uint64_t word0, uint8_t *d_info, uint8_t *d_cw, float *d_llr, double *d_h,
+                                      double *d_y, void *stream) {
+    if (int rc = polar_check_fading(kind, param)) return rc;
+    return polar_generate(c, kPolarChanFading + kind, snr_db, param, B, seed, word0, d_info, d_cw, d_llr, d_h, d_y,
+                          stream);
 }
 
 int bchk_polar_generate_device(bchk_polar *c, double snr_db, size_t B, uint64_t seed, uint64_t word0,
@@ -1228,11 +1274,12 @@ int bchk_polar_count_device(bchk_polar *c, const uint8_t *d_info_tx, const uint8
 // the records depend on the arguments only, not on `batch`.
 // q8: each batch's LLRs are quantised (scale, qmax) and decoded by the int8 kernel; the counters
 // still read the channel's f32 LLRs.
-static int polar_sweep(bchk_polar *c, int channel, double snr_from, double snr_step, int points, uint64_t max_words,
-                       uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out, double *seconds,
-                       uint64_t *words_decoded, bool q8, float scale, int qmax) {
-    // every point's parameter, before any work (only the BSC's has a range)
-    for (int pt = 0; pt < (channel == BCHK_CHANNEL_BSC && points > 0 ? points : 1); ++pt)
+static int polar_sweep(bchk_polar *c, int channel, double fpar, double snr_from, double snr_step, int points,
+                       uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch, bchk_polar_point *out,
+                       double *seconds, uint64_t *words_decoded, bool q8, float scale, int qmax) {
+    // every point's parameter, before any work (only the BSC's has a range); channel = kPolarChan*, a
+    // fading model and its fpar checked by the caller
+    for (int pt = 0; pt < (channel == BCHK_CHANNEL_BSC && points > 0 ? points : 1) && channel < kPolarChanFading; ++pt)
         if (int rc = polar_check_channel(channel, snr_from + pt * snr_step)) return rc;
     if (!c || !out) return pfail(BCHK_EINVAL, "NULL argument");
     if (q8 != c->is_q8())
@@ -1270,9 +1317,8 @@ static int polar_sweep(bchk_polar *c, int channel, double snr_from, double snr_s
         while (r.c[0] < max_words && r.c[1] < max_errors) {
             const size_t nb = (size_t)std::min<uint64_t>(Bm, max_words - r.c[0]);
             uint64_t h[8];
-            if ((rc = bchk_polar_generate_channel_device(c, channel, r.snr_db, nb, seed, word, (uint8_t *)c->txinfo.p,
-                                                         (uint8_t *)c->txcw.p, (float *)c->llr.p, nullptr, nullptr,
-                                                         s)))
+            if ((rc = polar_generate(c, channel, r.snr_db, fpar, nb, seed, word, (uint8_t *)c->txinfo.p,
+                                     (uint8_t *)c->txcw.p, (float *)c->llr.p, nullptr, nullptr, s)))
                 return rc;
             if (q8) {
                 if ((rc = bchk_polar_quantize_device(c, (const float *)c->llr.p, nb * N, scale, qmax, (int8_t *)c->q8.p,
@@ -1318,8 +1364,18 @@ static int polar_sweep(bchk_polar *c, int channel, double snr_from, double snr_s
 int bchk_polar_sweep_channel_device(bchk_polar *c, int channel, double snr_from, double snr_step, int points,
                                     uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
                                     bchk_polar_point *out, double *seconds, uint64_t *words_decoded) {
-    return polar_sweep(c, channel, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
+    if (int rc = polar_check_channel(channel, snr_from)) return rc;  // the id; polar_sweep checks every point
+    return polar_sweep(c, channel, 0.0, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
                        words_decoded, false, 0.0f, 0);
+}
+
+// The same loop over a fading model: the points are average Eb/N0 values in dB.
+int bchk_polar_sweep_fading_device(bchk_polar *c, int kind, double param, double snr_from, double snr_step, int points,
+                                   uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                   bchk_polar_point *out, double *seconds, uint64_t *words_decoded) {
+    if (int rc = polar_check_fading(kind, param)) return rc;
+    return polar_sweep(c, kPolarChanFading + kind, param, snr_from, snr_step, points, max_words, max_errors, seed,
+                       batch, out, seconds, words_decoded, false, 0.0f, 0);
 }
 
 // The same loop through the int8 decoder: generate -> quantize (scale, qmax) -> q8 decode -> count.
@@ -1327,8 +1383,18 @@ int bchk_polar_sweep_q8_device(bchk_polar *c, int channel, double snr_from, doub
                                uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
                                bchk_polar_point *out, double *seconds, uint64_t *words_decoded, float scale,
                                int qmax) {
-    return polar_sweep(c, channel, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
+    if (int rc = polar_check_channel(channel, snr_from)) return rc;  // the id; polar_sweep checks every point
+    return polar_sweep(c, channel, 0.0, snr_from, snr_step, points, max_words, max_errors, seed, batch, out, seconds,
                        words_decoded, true, scale, qmax);
+}
+
+int bchk_polar_sweep_q8_fading_device(bchk_polar *c, int kind, double param, double snr_from, double snr_step,
+                                      int points, uint64_t max_words, uint64_t max_errors, uint64_t seed, size_t batch,
+                                      bchk_polar_point *out, double *seconds, uint64_t *words_decoded, float scale,
+                                      int qmax) {
+    if (int rc = polar_check_fading(kind, param)) return rc;
+    return polar_sweep(c, kPolarChanFading + kind, param, snr_from, snr_step, points, max_words, max_errors, seed,
+                       batch, out, seconds, words_decoded, true, scale, qmax);
 }
 
 int bchk_polar_sweep_device(bchk_polar *c, double snr_from, double snr_step, int points, uint64_t max_words,
@@ -1420,11 +1486,11 @@ int bchk_polar_genie_device(bchk_polar *c, const uint8_t *d_info_tx, const float
     return 0;
 }
 
-// Words [word0, word0 + words) of the stream `seed` over `channel` at `param` through the genie
-// kernel, in batches; the sums are integers, so the result does not depend on `batch`.
-int bchk_polar_genie_run_channel(bchk_polar *c, int channel, double param, uint64_t words, uint64_t seed,
-                                 uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds) {
-    if (int rc = polar_check_channel(channel, param)) return rc;
+// Words [word0, word0 + words) of the stream `seed` over `channel` (kPolarChan*, checked by the
+// caller) at `param` (and fpar, polar_generate) through the genie kernel, in batches; the sums are
+// integers, so the result does not depend on `batch`.
+static int polar_genie_run(bchk_polar *c, int channel, double param, double fpar, uint64_t words, uint64_t seed,
+                           uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds) {
     if (!c || !err || !soft) return pfail(BCHK_EINVAL, "NULL argument");
     if (words == 0 || words > (1ull << 31))
         return pfail(BCHK_EINVAL, "words must be 1..2^31 (the soft sums stay inside 64 bits)");
@@ -1451,8 +1517,8 @@ int bchk_polar_genie_run_channel(bchk_polar *c, int channel, double param, uint6
     PHIP_TRY(hipMemsetAsync(c->gsum.p, 0, 16 * U, s));
     for (uint64_t done = 0; done < words;) {
         const size_t nb = (size_t)std::min<uint64_t>(Bm, words - done);
-        if ((rc = bchk_polar_generate_channel_device(c, channel, param, nb, seed, word0 + done, (uint8_t *)c->txinfo.p,
-                                                     nullptr, (float *)c->llr.p, nullptr, nullptr, s)) ||
+        if ((rc = polar_generate(c, channel, param, fpar, nb, seed, word0 + done, (uint8_t *)c->txinfo.p, nullptr,
+                                 (float *)c->llr.p, nullptr, nullptr, s)) ||
             (rc = bchk_polar_genie_device(c, (const uint8_t *)c->txinfo.p, (const float *)c->llr.p, nb, d_err, d_soft,
                                           nullptr, nullptr, s)))
             return rc;
@@ -1465,6 +1531,18 @@ int bchk_polar_genie_run_channel(bchk_polar *c, int channel, double param, uint6
     memcpy(soft, h.data() + U, 8 * U);
     if (seconds) *seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return 0;
+}
+
+int bchk_polar_genie_run_channel(bchk_polar *c, int channel, double param, uint64_t words, uint64_t seed,
+                                 uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds) {
+    if (int rc = polar_check_channel(channel, param)) return rc;
+    return polar_genie_run(c, channel, param, 0.0, words, seed, word0, batch, err, soft, seconds);
+}
+
+int bchk_polar_genie_run_fading(bchk_polar *c, int kind, double param, double snr_db, uint64_t words, uint64_t seed,
+                                uint64_t word0, size_t batch, uint64_t *err, int64_t *soft, double *seconds) {
+    if (int rc = polar_check_fading(kind, param)) return rc;
+    return polar_genie_run(c, kPolarChanFading + kind, snr_db, param, words, seed, word0, batch, err, soft, seconds);
 }
 
 int bchk_polar_genie_run(bchk_polar *c, double snr_db, uint64_t words, uint64_t seed, uint64_t word0, size_t batch,
